@@ -18,13 +18,26 @@ resident in HBM when the timed region starts):
                 inputs (13 B .. 45 KB) and C1 through the host API, next to README.md:88-94.
 A step encodes the batch (mib_ctx_encode: packed compressed streams in HBM), gathers the
 compressed shards to rank 0 over RCCL (N > 1, c3/c4; the only collective)
-and decodes them back (mib_ctx_decode) into HBM.  The round trip is checked bit-exact on
-device after the warmup steps (outside the timed region).
+and decodes them back (mib_ctx_decode) into HBM.  After the warmup steps (outside the timed
+region) the statuses and sizes the decode returned are checked; --full also compares the
+decoded bytes with the inputs on the device.
   value = uncompressed MB (10^6 B) processed by all ranks / step time (max over ranks).
+  ms_per_step = the time of the timed region / --steps.
   scaling "weak": per-GPU work fixed as N grows.
 
 Launch: python bench.py [--gpus N --steps K --warmup W --workload c4|c3|c2]; N > 1 via
 torch.distributed.run (one rank per GPU, backend nccl = RCCL).
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what
+the headline figure does not need, each outside the timed region: the bit-exact comparison,
+the cpu_baseline and ratio_same_sample below, the encoder's kernel table (one more step with
+events on every kernel), the ref leg's all-streams call, the in-library leg's one-context
+batch.  Without it those fields are null and kernel_ms_per_step holds only the kernels the
+timed steps' events covered.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(compressed streams and their offsets, decoded bytes, sizes and statuses; see dump_outputs).
+The inputs are seeded, so two runs with the same arguments encode the same bytes.
 
 roofline: the step's dominant kernel (largest device time, HIP events recorded by the
 library on the launch stream); achieved = algorithmic bytes of one launch (input + output
@@ -83,7 +96,55 @@ def parse():
     ap.add_argument('--stream-chunk', type=int, default=32, help='c5: BrotliEncoder streamChunk in MiB (0: the reference\'s cadence)')
     ap.add_argument('--gpus-in-lib', type=int, default=0,
                     help='host-API leg: the batch through mib_*_batch_n with N shards against the one-context batch')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: the bit-exact round-trip check, the CPU baseline and '
+                         'the compressed-size comparison on the same sample, the encoder\'s kernel table (one '
+                         'untimed step of its own), and each leg\'s side measurements')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last step returned to DIR/<name>.npy')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    args.cpu = args.full and not args.no_cpu_baseline
+    return args
+
+
+# --dump-outputs: what the last timed step handed its caller, as float arrays.  Lists of
+# offsets, sizes and statuses are written whole (float64: exact to 2^53); byte buffers as
+# float32, whole when they fit their share of DUMP_SAMPLE_BYTES, else at fixed positions: one
+# per equal stratum of the buffer, its offset inside the stratum drawn from a generator seeded
+# with DUMP_SEED + the buffer's index.  The positions depend on the buffer's length only, so two
+# builds that return the same bytes write the same files.
+DUMP_SAMPLE_BYTES = 48 * 10 ** 6
+DUMP_SEED = 20240
+
+
+def sample_positions(n, m, seed):
+    import numpy as np
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    edges = (np.arange(m + 1, dtype=np.int64) * n) // m
+    return edges[:-1] + np.random.default_rng(seed).integers(0, edges[1:] - edges[:-1])
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """arrays: name -> list of numbers | bytes | 1-D uint8 torch tensor (host or device)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = '' if world == 1 else '_rank%d' % rank
+    nbuf = sum(1 for a in arrays.values() if not isinstance(a, (list, tuple)))
+    per = DUMP_SAMPLE_BYTES // max(1, world) // 4 // max(1, nbuf)
+    for idx, (name, a) in enumerate(arrays.items()):
+        if isinstance(a, (list, tuple)):
+            v = np.asarray(a, dtype=np.float64)
+        else:
+            pos = sample_positions(len(a), per, DUMP_SEED + idx)
+            if hasattr(a, 'device'):
+                import torch
+                v = a[torch.from_numpy(pos).to(a.device)].cpu().numpy().astype(np.float32)
+            else:
+                v = np.frombuffer(a, dtype=np.uint8)[pos].astype(np.float32)
+        np.save(os.path.join(out_dir, name + suffix + '.npy'), v)
 
 
 def cpu_share():
@@ -266,9 +327,13 @@ def run_stream(args, rank, world, local):
         out = brotli_amd.brotliDecode(stream, {'customDictionary': cdict})
     t2 = time.perf_counter()
     times = brotli_amd.default_kernel_times()   # (the decoder's: the timed region)
-    brotli_amd.default_profiling(True)
-    enc()   # (untimed: the encoder's kernel table, one step)
-    enc_times = brotli_amd.default_kernel_times()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'compressed': stream, 'decoded': out}, rank, world)
+    enc_times = {}
+    if args.full:
+        brotli_amd.default_profiling(True)
+        enc()   # (untimed: the encoder's kernel table, one step)
+        enc_times = brotli_amd.default_kernel_times()
     brotli_amd.default_profiling(False)
     assert out == data
     del out
@@ -289,7 +354,7 @@ def run_stream(args, rank, world, local):
         avg_ms = dom_ms / max(1, dom_n)
         achieved = launch_bytes / (avg_ms * 1e-3) / 1e9
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu:
             # decode: the oracle (reference decoder restated) decodes the same stream with the
             # same dictionary on one host thread (it is one bit-serial stream).  encode: the
             # oracle's restatement of the reference's q9 path (hash chains + greedy,
@@ -337,8 +402,8 @@ def run_stream(args, rank, world, local):
             'compressed_ratio': round(len(stream) / size, 5),
             'kernel_ms_per_step': dict(sorted(list({n: round(v[0] / args.steps, 3) for n, v in times.items()}.items()) +
                                               list({n: round(v[0], 3) for n, v in enc_times.items()}.items()))),
-            'kernel_times_from': 'decoder: the timed decode loop; encoder: one untimed encode step after it (the '
-                                 'timed encode loop runs without kernel events)',
+            'kernel_times_from': 'decoder: the timed decode loop; encoder: %s (the timed encode loop runs without '
+                                 'kernel events)' % ('one untimed encode step after it' if args.full else 'with --full'),
             'roofline': {'bound': 'hbm', 'kernel': dom_name, 'achieved': round(achieved, 3), 'peak': PEAK_HBM_GBS,
                          'unit': 'GB/s', 'frac': round(achieved / PEAK_HBM_GBS, 6),
                          'traffic': load_traffic(dom_name, 'c5' if args.stream_chunk else 'c5cad'),
@@ -370,6 +435,7 @@ def run_latency(args):
     from brotli_amd import datagen
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     rows = []
+    dump = {}
     reps = max(1, args.steps) * 20
     for name, make, ref_ms in LATENCY_INPUTS:
         data = make() if make else datagen.enwik_text(45000, 1)
@@ -386,11 +452,13 @@ def run_latency(args):
             te.append(t1 - t0)
             td.append(t2 - t1)
         assert out == data
+        dump['compressed_%d' % len(rows)] = enc
+        dump['decoded_%d' % len(rows)] = out
         row = {'input': name, 'bytes': len(data), 'compressed': len(enc),
                'encode_ms_median': round(statistics.median(te) * 1e3, 4),
                'decode_ms_median': round(statistics.median(td) * 1e3, 4),
                'ref_encode_ms_published': ref_ms}
-        if not args.no_cpu_baseline:
+        if args.cpu:
             import _oracle
             t0 = time.perf_counter()
             n = 0
@@ -402,8 +470,10 @@ def run_latency(args):
         rows.append(row)
     tot_b = sum(r['bytes'] for r in rows)
     tot_s = sum((r['encode_ms_median'] + r['decode_ms_median']) * 1e-3 for r in rows)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dump)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.cpu:
         cpu = {'value': round(tot_b / 1e6 / sum(r['oracle_encode_ms'] * 1e-3 for r in rows), 4), 'unit': 'MB/s',
                'cores': 1, 'kind': 'port',
                'sample': 'the same inputs, one oracle q11 encode per call on one host thread (encode only)'}
@@ -442,7 +512,7 @@ def run_ref(args):
         if n <= 0:
             n = len(brotli_amd.brotliDecode(enc))
         streams.append((name, m2, host, enc, n))
-    per = []
+    per, dump = [], {}
     tot_out, tot_s = 0, 0.0
     for name, m2, host, enc, n in streams:
         src = torch.tensor(list(enc), dtype=torch.uint8, device=dev)
@@ -460,26 +530,31 @@ def run_ref(args):
         dt = (time.perf_counter() - t0) / args.steps
         tot_out += n
         tot_s += dt
+        dump['decoded_' + name] = out[:n]
         per.append({'stream': name, 'out_bytes': n, 'in_bytes': len(enc), 'ms': round(dt * 1e3, 3),
                     'kernel_ms': round(kern / args.steps, 3), 'MBps': round(n / dt / 1e6, 2),
                     'ref_ms_m2max': m2, 'ref_ms_survey_host': host})
-    # all streams in one call (one wave each)
-    cat = b''.join(s[3] for s in streams)
-    ioff, ooff = [0], [0]
-    for s_ in streams:
-        ioff.append(ioff[-1] + len(s_[3]))
-        ooff.append(ooff[-1] + s_[4] + 4096)
-    src = torch.tensor(list(cat), dtype=torch.uint8, device=dev)
-    out = torch.empty(ooff[-1], dtype=torch.uint8, device=dev)
-    ctx.decode(src.data_ptr(), ioff, out.data_ptr(), ooff)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dump)
+    batch_ms = None
+    if args.full:
+        # all streams in one call (one wave each)
+        cat = b''.join(s[3] for s in streams)
+        ioff, ooff = [0], [0]
+        for s_ in streams:
+            ioff.append(ioff[-1] + len(s_[3]))
+            ooff.append(ooff[-1] + s_[4] + 4096)
+        src = torch.tensor(list(cat), dtype=torch.uint8, device=dev)
+        out = torch.empty(ooff[-1], dtype=torch.uint8, device=dev)
         ctx.decode(src.data_ptr(), ioff, out.data_ptr(), ooff)
-    torch.cuda.synchronize()
-    batch_ms = (time.perf_counter() - t0) / args.steps * 1e3
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            ctx.decode(src.data_ptr(), ioff, out.data_ptr(), ooff)
+        torch.cuda.synchronize()
+        batch_ms = round((time.perf_counter() - t0) / args.steps * 1e3, 3)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.cpu:
         import _oracle
         t0 = time.perf_counter()
         for s_ in streams:
@@ -494,7 +569,7 @@ def run_ref(args):
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'u8', 'data': 'reference fixtures',
         'config': {'workload': 'decode of the reference bench streams (tests/golden/bench/*.br), one stream per call, '
                                'input/output in HBM', 'name': 'ref', 'parallelism': 'replicas1'},
-        'streams': per, 'all_streams_one_call_ms': round(batch_ms, 3), 'roofline': None, 'cpu_baseline': cpu}),
+        'streams': per, 'all_streams_one_call_ms': batch_ms, 'roofline': None, 'cpu_baseline': cpu}),
           flush=True)
 
 
@@ -522,8 +597,10 @@ def run_in_lib(args):
         out = brotli_amd.decode_batch(comp, gpus=gpus)
         return comp, out
 
+    # the one-context batch is the comparison: with --full only
+    legs = (None, n) if args.full else (n,)
     ref_comp = None
-    for g in (None, n):
+    for g in legs:
         for _ in range(max(1, args.warmup)):
             comp, out = leg(g)
             if out != bufs:
@@ -534,9 +611,9 @@ def run_in_lib(args):
                 raise SystemExit('in-library leg: sharded streams differ from the one-context batch')
     res = {}
     del comp, out
-    for g in (None, n):
+    for g in legs:
         te = td = 0.0
-        for _ in range(args.steps):
+        for it in range(args.steps):
             t0 = time.perf_counter()
             comp = brotli_amd.encode_batch(bufs, opts, gpus=g)
             t1 = time.perf_counter()
@@ -544,13 +621,16 @@ def run_in_lib(args):
             t2 = time.perf_counter()
             te += t1 - t0
             td += t2 - t1
+            if args.dump_outputs and g == n and it == args.steps - 1:
+                dump_outputs(args.dump_outputs, {'compressed': b''.join(comp), 'compressed_sizes': [len(c) for c in comp],
+                                                 'decoded': b''.join(out), 'decoded_sizes': [len(o) for o in out]})
             # (the caller's results are freed outside the timed calls: releasing 1,024 x 1 MiB
             # bytes objects took Python 57-108 ms on the MI355X box, scripts/host_xfer_probe.py)
             del comp, out
         res['one_context' if g is None else 'shards'] = {'encode_ms': round(te * 1e3 / args.steps, 3),
                                                          'decode_ms': round(td * 1e3 / args.steps, 3)}
-    one = res['one_context']['encode_ms'] + res['one_context']['decode_ms']
     sh = res['shards']['encode_ms'] + res['shards']['decode_ms']
+    one = res['one_context']['encode_ms'] + res['one_context']['decode_ms'] if args.full else None
     total = k * size
     print(json.dumps({
         'metric': 'encode+decode MB/s at q11 lgwin=22, host buffers through the sharded C-ABI batch calls',
@@ -560,7 +640,7 @@ def run_in_lib(args):
         'config': {'workload': '%s batch (%d x %d B) as host buffers: mib_encode_batch_n + mib_decode_batch_n with %d '
                                'shards on device 0 vs mib_encode_batch + mib_decode_batch (PCIe included)'
                                % (wl, k, size, n), 'name': 'in_lib', 'shards': n, 'parallelism': 'shards%d_on_1gpu' % n},
-        'legs': res, 'shard_overhead': round(sh / one - 1.0, 4), 'roofline': None, 'cpu_baseline': None}), flush=True)
+        'legs': res, 'shard_overhead': round(sh / one - 1.0, 4) if one else None, 'roofline': None, 'cpu_baseline': None}), flush=True)
 
 
 def datagen_device(total, seed, dev):
@@ -636,8 +716,10 @@ def main():
     for w in range(max(1, args.warmup)):
         out_off, sizes, status = step({})
     torch.cuda.synchronize()
+    # what decode returned says whether every stream decoded to its length; the bytes
+    # themselves are compared with --full
     bad = [i for i in range(k) if status[i] != 0 or sizes[i] != size]
-    if bad or not torch.equal(dec.view(k, slot)[:, :size], data.view(k, size)):
+    if bad or (args.full and not torch.equal(dec.view(k, slot)[:, :size], data.view(k, size))):
         raise SystemExit('round trip FAILED on rank %d: %d bad streams' % (rank, len(bad)))
     comp_bytes = out_off[-1]
     gpu_sizes = [out_off[i + 1] - out_off[i] for i in range(k)]
@@ -658,7 +740,12 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     timed = set(times)   # (the kernels the timed steps' events measured: the roofline's candidates)
-    if args.kernel_events == 'decode':   # the encoder's kernel table: one untimed step, scaled
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {
+            'compressed': comp[:out_off[-1]], 'compressed_offsets': out_off,
+            'decoded': dec.view(k, slot)[:, :size].reshape(-1), 'decoded_sizes': sizes, 'decode_status': status},
+            rank, world)
+    if args.full and args.kernel_events == 'decode':   # the encoder's kernel table: one untimed step, scaled
         ctx.set_profiling(True)
         extra = {}
         step(extra)
@@ -677,7 +764,7 @@ def main():
         comp_all = comp_bytes
 
     cpu, ratios = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu:
         # the CPU sample: the first buffers of the same batch (C2: 1 MiB slices of its one buffer)
         piece = min(size, MIB)
         nsamp = min(max(1, total // piece), 16 * cpu_share())
@@ -728,8 +815,9 @@ def main():
             'vs_baseline': None,
             'dtype': 'u8',
             'data': 'synthetic',
-            'config': {'workload': desc + ', encode -> %sdecode round trip (bit-exact checked)' % (
-                           'RCCL gather -> ' if gather else ''),
+            'config': {'workload': desc + ', encode -> %sdecode round trip (%s)' % (
+                           'RCCL gather -> ' if gather else '',
+                           'bit-exact checked' if args.full else 'statuses and sizes checked'),
                        'name': wl, 'streams_per_gpu': k, 'bytes_per_stream': size, 'quality': args.quality,
                        'lgwin': args.lgwin, 'mode': mode,
                        'parallelism': ('shard%d' % world) if k > 1 else ('replicas%d' % world)},
@@ -739,6 +827,7 @@ def main():
             'ratio_same_sample': ratios,
             'kernel_ms_per_step': {n: round(v[0] / args.steps, 3) for n, v in sorted(times.items())},
             'kernel_events': args.kernel_events,
+            'full': args.full,
             'roofline': {'bound': 'hbm', 'kernel': dom_name, 'achieved': round(achieved, 3), 'peak': PEAK_HBM_GBS,
                          'unit': 'GB/s', 'frac': round(achieved / PEAK_HBM_GBS, 6),
                          'traffic': load_traffic(dom_name, wl),

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 TAG=$1
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-A="--steps 3 --warmup 1 --no-cpu-baseline"
+A="--steps 3 --warmup 1 --full --no-cpu-baseline"
 run() {   # name, env..., -- bench args
   local name=$1; shift
   env "$@" timeout -k 10 300 python3 bench.py $A > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail $OUT/$name.err; exit 1; }
