@@ -430,6 +430,54 @@ static napi_value js_woff2(napi_env env, napi_callback_info info, int hmtx) {
 }
 static napi_value js_woff2_glyf(napi_env env, napi_callback_info info) { return js_woff2(env, info, 0); }
 static napi_value js_woff2_hmtx(napi_env env, napi_callback_info info) { return js_woff2(env, info, 1); }
+/* woff2InvGlyf(data) -> [glyf, loca] (Buffers): the TrueType tables of a WOFF2-transformed glyf
+ * table, computed on the GPU; a table that does not parse throws (MIB_E_INVALID_ARG) */
+static napi_value js_woff2_inv_glyf(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  const uint8_t *p;
+  size_t n;
+  if (argc < 1 || get_bytes(env, argv[0], &p, &n)) {
+    napi_throw_type_error(env, NULL, "input must be a Uint8Array");
+    return NULL;
+  }
+  mib_buf glyf = {0, 0}, loca = {0, 0};
+  const int rc = mib_woff2_reconstruct_glyf(p, n, &glyf, &loca);
+  if (rc) return throw_code(env, rc);
+  napi_value arr, g, l;
+  g = take(env, &glyf);
+  if (!g) {
+    mib_buf_free(&loca);
+    return NULL;
+  }
+  l = take(env, &loca);
+  if (!l) return NULL;
+  CHECK(env, napi_create_array_with_length(env, 2, &arr));
+  CHECK(env, napi_set_element(env, arr, 0, g));
+  CHECK(env, napi_set_element(env, arr, 1, l));
+  return arr;
+}
+/* woff2InvHmtx(data, glyf, loca, numGlyphs, numHMetrics) -> Buffer: the hmtx table of a
+ * WOFF2-transformed one, the dropped side bearings from the glyphs' xMin */
+static napi_value js_woff2_inv_hmtx(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  const uint8_t *p[3];
+  size_t n[3];
+  if (argc < 5 || get_bytes(env, argv[0], &p[0], &n[0]) || get_bytes(env, argv[1], &p[1], &n[1]) ||
+      get_bytes(env, argv[2], &p[2], &n[2])) {
+    napi_throw_type_error(env, NULL, "data, glyf and loca must be Uint8Arrays");
+    return NULL;
+  }
+  const int64_t ng = get_i64(env, argv[3], -1), nhm = get_i64(env, argv[4], -1);
+  if (ng < 0 || nhm < 0 || ng > 0xFFFFFFFFll || nhm > 0xFFFFFFFFll) return throw_code(env, MIB_E_INVALID_ARG);
+  mib_buf b = {0, 0};
+  const int rc = mib_woff2_reconstruct_hmtx(p[0], n[0], p[1], n[1], p[2], n[2], (uint32_t)ng, (uint32_t)nhm, &b);
+  if (rc) return throw_code(env, rc);
+  return take(env, &b);
+}
 static napi_value js_encode_batch_async(napi_env env, napi_callback_info info) { return start_async(env, info, 0); }
 static napi_value js_decode_batch_async(napi_env env, napi_callback_info info) { return start_async(env, info, 1); }
 
@@ -446,6 +494,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"decodeBatchAsync", 0, js_decode_batch_async, 0, 0, 0, napi_default, 0},
       {"woff2Glyf", 0, js_woff2_glyf, 0, 0, 0, napi_default, 0},
       {"woff2Hmtx", 0, js_woff2_hmtx, 0, 0, 0, napi_default, 0},
+      {"woff2InvGlyf", 0, js_woff2_inv_glyf, 0, 0, 0, napi_default, 0},
+      {"woff2InvHmtx", 0, js_woff2_inv_hmtx, 0, 0, 0, napi_default, 0},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

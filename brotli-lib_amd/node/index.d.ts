@@ -56,3 +56,7 @@ export declare function brotliDecodeBatchAsync(inputs: Uint8Array[], options?: B
 export declare function woff2TransformGlyf(ttf: Uint8Array): Uint8Array
 /** WOFF2 'hmtx' transform (section 5.4), or null when the table must stay untransformed */
 export declare function woff2TransformHmtx(ttf: Uint8Array): Uint8Array | null
+/** inverse of woff2TransformGlyf: the TrueType glyf table and its loca (the header's indexFormat), on the GPU; throws on a table that does not parse */
+export declare function woff2ReconstructGlyf(data: Uint8Array): { glyf: Uint8Array, loca: Uint8Array }
+/** inverse of woff2TransformHmtx: the dropped side bearings are the glyphs' xMin in glyf / loca */
+export declare function woff2ReconstructHmtx(data: Uint8Array, glyf: Uint8Array, loca: Uint8Array, numGlyphs: number, numHMetrics: number): Uint8Array

@@ -110,9 +110,18 @@ function woff2TransformHmtx(ttf) {
   const r = native.woff2Hmtx(ttf)
   return r === null ? null : toU8(r)
 }
+// the WOFF2 reader's step after brotliDecode: the TrueType glyf / loca / hmtx tables of the
+// transformed ones, computed on the GPU (the bytes fontTools reconstructs)
+function woff2ReconstructGlyf(data) {
+  const [glyf, loca] = native.woff2InvGlyf(data)
+  return { glyf: toU8(glyf), loca: toU8(loca) }
+}
+function woff2ReconstructHmtx(data, glyf, loca, numGlyphs, numHMetrics) {
+  return toU8(native.woff2InvHmtx(data, glyf, loca, numGlyphs, numHMetrics))
+}
 
 module.exports = {
   brotliEncode, BrotliEncoder, brotliDecode, brotliDecodedSize, EncoderMode,
   brotliEncodeBatch, brotliEncodeBatchAsync, brotliDecodeBatchAsync,
-  woff2TransformGlyf, woff2TransformHmtx,
+  woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx,
 }

@@ -147,6 +147,11 @@ def _L():
         lib.mib_ctx_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int]
         lib.mib_woff2_transform_glyf.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
         lib.mib_woff2_transform_hmtx.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
+        lib.mib_woff2_reconstruct_glyf.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Buf),
+                                                   ctypes.POINTER(_Buf)]
+        lib.mib_woff2_reconstruct_hmtx.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                                   ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                                                   ctypes.POINTER(_Buf)]
         lib.mib_part_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         lib.mib_default_ctx.restype = ctypes.c_void_p
         lib.mib_ctx_clear_times.argtypes = [ctypes.c_void_p]
@@ -366,6 +371,34 @@ def woff2_transform_hmtx(ttf):
     if not buf.size:
         _L().mib_buf_free(ctypes.byref(buf))
         return None
+    return _take(buf)
+
+
+def woff2_reconstruct_glyf(data):
+    """(glyf, loca): the TrueType tables a WOFF2-transformed 'glyf' table stands for (W3C WOFF2
+    sections 5.1, 5.3), computed on the GPU, byte for byte as fontTools reconstructs and compiles
+    them (4-byte padding; loca in the header's indexFormat).  The input is untrusted: a table
+    that does not parse raises BrotliError (MIB_E_INVALID_ARG)."""
+    data = _bytes(data)
+    glyf, loca = _Buf(), _Buf()
+    rc = _L().mib_woff2_reconstruct_glyf(data, len(data), ctypes.byref(glyf), ctypes.byref(loca))
+    if rc:
+        raise _err(rc)
+    return _take(glyf), _take(loca)
+
+
+def woff2_reconstruct_hmtx(data, glyf, loca, num_glyphs, num_hmetrics):
+    """The 'hmtx' table of a WOFF2-transformed one (section 5.4), computed on the GPU: the side
+    bearings the transform dropped are the glyphs' xMin in `glyf` / `loca` (as
+    woff2_reconstruct_glyf returns them)."""
+    data, glyf, loca = _bytes(data), _bytes(glyf), _bytes(loca)
+    if not 0 <= int(num_glyphs) <= 0xFFFFFFFF or not 0 <= int(num_hmetrics) <= 0xFFFFFFFF:
+        raise _err(-101)   # MIB_E_INVALID_ARG
+    buf = _Buf()
+    rc = _L().mib_woff2_reconstruct_hmtx(data, len(data), glyf, len(glyf), loca, len(loca), int(num_glyphs),
+                                         int(num_hmetrics), ctypes.byref(buf))
+    if rc:
+        raise _err(rc)
     return _take(buf)
 
 

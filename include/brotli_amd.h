@@ -179,6 +179,20 @@ int mib_woff2_transform_glyf(const uint8_t *ttf, size_t n, mib_buf *out);
  * Returns 0 with out->size = 0 when both arrays differ (no transform: the table is stored
  * as is).  The transformed loca table is empty (WOFF2 section 5.3): nothing to compute. */
 int mib_woff2_transform_hmtx(const uint8_t *ttf, size_t n, mib_buf *out);
+/* Inverse of mib_woff2_transform_glyf (W3C WOFF2 section 5.1, 5.3): the transformed glyf table
+ * becomes a TrueType glyf table and its loca table (format = the header's indexFormat), byte
+ * for byte what fontTools' WOFF2GlyfTable.reconstruct + compile (4-byte padding, boxes kept)
+ * and WOFF2LocaTable.compile produce.  The bytes are untrusted: MIB_E_INVALID_ARG for a header
+ * that does not add up, a glyph that runs past a stream, streams not used up exactly, a
+ * composite without its box, or offsets that loca format 0 cannot hold. */
+int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_buf *glyf, mib_buf *loca);
+/* Inverse of mib_woff2_transform_hmtx (section 5.4): advance widths plus the side bearings, the
+ * dropped array(s) taken from the glyphs' xMin in `glyf` / `loca` (0 for an empty glyph).
+ * loca's format follows from loca_n.  MIB_E_INVALID_ARG for reserved flag bits, flags that
+ * drop neither array, and a size that is not exactly what the flags imply. */
+int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const uint8_t *glyf, size_t glyf_n,
+                               const uint8_t *loca, size_t loca_n, uint32_t num_glyphs,
+                               uint32_t num_hmetrics, mib_buf *out);
 
 /* Part-parallel decoding (streams this encoder marked with a part index):
  * how many streams a context (NULL: the default one) decoded part-parallel, and how many of
