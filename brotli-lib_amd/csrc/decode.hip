@@ -54,15 +54,18 @@ constexpr int kBlockTreesCap = 3091;   // engine.ts:163 Int32Array(3091)
 
 // LDS working set of one stream (one wave): the state below (~14 KiB) plus a table area
 // declared by the kernel itself: 12,224 entries in the batch build (40 KiB per stream, four
-// streams per CU), 68,096 in the one-per-CU build a call with few streams gets, which also
+// streams per CU), 65,536 in the one-per-CU build a call with few streams gets, which also
 // keeps the block-type trees in LDS -- so a foreign stream's large prefix-code set (native
 // brotli's q11 fonts: 142 literal codes in a metablock) stays in LDS.  (The table area is
 // static in both builds: a dynamically sized one made the batch decode 14 % slower, 179 vs
 // 157 ms on C4.)  A metablock's tables are built in HBM scratch (packed, exact sizes) and,
 // when they fit, copied into the table area as 16-bit entries (nbits << 12 |
-// symbol-or-subtable-offset), tree roots resolved to absolute indices.
+// symbol-or-subtable-offset), tree roots resolved to absolute indices.  A root is itself a
+// 16-bit entry of the area, so the area ends where 16 bits stop addressing: with more entries
+// (it was 68,096 once) a metablock of 65,537.. entries went to LDS with its last roots wrapped.
 constexpr int kLdsTab = 12224;   // the batch build's table area (4 streams per CU)
-constexpr int kLdsTabBig = 68096;   // the one-stream-per-CU build's
+constexpr int kLdsTabBig = 65536;   // the one-stream-per-CU build's
+static_assert(kLdsTab <= 65536 && kLdsTabBig <= 65536, "every root (an absolute index below the total) must fit uint16_t");
 
 typedef __attribute__((address_space(1))) uint8_t GU8;          // HBM
 typedef const __attribute__((address_space(1))) int32_t GI32;

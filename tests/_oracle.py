@@ -119,3 +119,10 @@ def max_block_types():
     out = (ctypes.c_int * 3)()
     lib().oracle_max_block_types(out)
     return list(out)
+
+
+def max_table_total():
+    """the largest total of one metablock's literal, command and distance tree groups (their
+    roots and tables, in entries) the oracle decoder has built on this thread since the last call"""
+    lib().oracle_max_table_total.restype = ctypes.c_int
+    return lib().oracle_max_table_total()
