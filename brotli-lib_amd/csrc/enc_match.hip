@@ -2,6 +2,7 @@
 // hash buckets (laid out as flat chains by the bucket sort, enc_sort.hip).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "enc_common.h"
 
@@ -17,8 +18,26 @@ namespace enc {
 // HBM unless a match reaches 32 bytes; only such matches extend through global memory.  The
 // staircase of strictly increasing lengths (shortest distance for each length) is kept,
 // longest last.
+//
+// The record of position g, exactly (tests/test_gpu_match_records.py restates these rules):
+//  1. its candidates are the earlier positions of the same stream with the same bucket key
+//     (hashn over hash_bytes bytes: collisions included), nearest first; at most
+//     min(depth, kBack) are examined, and the walk ends before the first one farther than
+//     max_dist = (1 << lgwin) - 16;
+//  2. a candidate's length is the common prefix, capped at the bytes left in g's 64 KiB parse
+//     segment (or the stream) and at kMatchLenSat = 255 (a part index caps it further);
+//  3. it is taken iff that length exceeds `best`, which starts at 3 and becomes the length;
+//  4. the last kMaxMatches taken are kept as (length << 24 | distance), longest last, zeros
+//     after them;
+//  5. the walk ends after a take that reaches the cap of rule 2;
+//  6. positions with fewer than hash_bytes bytes left (invalid key) have an empty record.
 constexpr int kBack = 64;
 constexpr int kPreW = 4;   // staged prefix: 4 x 8 bytes
+// steps per window of the walk (window_walk): 7, 9, 21 or 63 (MIB_FM_WIN: experiment builds)
+#ifndef MIB_FM_WIN
+#define MIB_FM_WIN 9
+#endif
+constexpr int kWin = MIB_FM_WIN;
 
 // 32 bytes at p as four little-endian 64-bit words (zero past avail)
 __device__ __forceinline__ void load_prefix32(const uint8_t *p, uint32_t avail, uint64_t *o) {
@@ -42,6 +61,195 @@ __device__ __forceinline__ void load_prefix32(const uint8_t *p, uint32_t avail, 
 #pragma unroll
   for (int i = 0; i < kPreW; i++) o[i] = 0;
   for (uint32_t i = 0; i < avail && i < 8 * kPreW; i++) o[i >> 3] |= (uint64_t)p[i] << (8 * (i & 7));
+}
+
+// The staircase during the walk: right-aligned (a take shifts every word down one and enters
+// at the top -- no count, no selects; a full one drops its shortest entry that way), and
+// left-aligned once before the record is stored (valid entries first, zeros after).
+__device__ __forceinline__ void stair_push(uint32_t (&s)[kMaxMatches], uint32_t m) {
+#pragma unroll
+  for (int q = 1; q < kMaxMatches; q++) s[q - 1] = s[q];
+  s[kMaxMatches - 1] = m;
+}
+__device__ __forceinline__ void stair_left_align(uint32_t (&s)[kMaxMatches]) {
+  // (a match word is never 0 and the empty words lead: word sh - 1 empty = at least sh empty)
+#pragma unroll
+  for (int sh = 4; sh >= 1; sh >>= 1) {
+    if (sh >= kMaxMatches) continue;
+    const bool mv = s[sh - 1] == 0;
+#pragma unroll
+    for (int q = 0; q < kMaxMatches; q++) s[q] = mv ? (q + sh < kMaxMatches ? s[q + sh] : 0u) : s[q];
+  }
+}
+
+typedef const __attribute__((address_space(1))) uint8_t GU8;
+__device__ __forceinline__ uint32_t load_u32_global(GU8 *p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+// match_len (enc_common.h) through global loads: the stream bytes are device memory, and a
+// flat load also counts on lgkmcnt, which the walk's LDS reads wait for
+__device__ __forceinline__ uint32_t match_len_global(GU8 *a, GU8 *b, uint32_t limit) {
+  uint32_t m = 0;
+  while (m + 4 <= limit) {
+    const uint32_t x = load_u32_global(a + m) ^ load_u32_global(b + m);
+    if (x) return m + (__ffs(x) - 1) / 8;
+    m += 4;
+  }
+  while (m < limit && a[m] == b[m]) m++;
+  return m;
+}
+
+// The walk over the staged window, one function for every build of the kernel: entry `me`
+// against the nwalk entries before it in its run, nearest first; takes go to `best` and the
+// (right-aligned) staircase.  Returns `stop`: the walk ended at a candidate beyond the
+// window or a copy reached its limit, so no farther candidate (the history part) can matter.
+//
+// A candidate is screened by one staged word before the exact tests: it can only be longer
+// than best if it matches byte `best`, so the word that holds that byte is compared under a
+// mask of its bytes up to that one (word 0 and four bytes at the start, when best = 3).  Most
+// candidates fail the screen.  The steps are wave-uniform (t is a scalar, the run's end per
+// lane a compare, not a divergent exit) and come in windows, see below.  (As one per-lane loop
+// with break / continue every candidate paid the exit-mask bookkeeping of the rare paths, ~48
+// instructions, r05 ISA listing; as a per-lane skip loop the lanes' different skip lengths
+// multiplied the steps.)
+template <bool kParts, int kN>
+__device__ __forceinline__ bool window_walk(const uint64_t (*spre)[kN], const uint32_t *spos, int me, int nwalk, uint32_t g,
+                                            uint32_t limit, uint32_t max_dist, const uint8_t *cur, bool parts, uint32_t pA,
+                                            uint32_t pbits, uint32_t plag, uint32_t &best, uint32_t (&stair)[kMaxMatches]) {
+  typedef const __attribute__((address_space(3))) uint64_t LU64;
+  // The screen's state: the staged word that holds byte `best` (word sw, the last one from 32
+  // bytes on), a mask k of its bytes up to byte `best`, and mine of it under that mask: a
+  // candidate's word c passes iff (c & k) == mk.
+  const uint32_t a_me = (uint32_t)(uintptr_t)(LU64 *)&spre[0][me];
+  const uint64_t mine0 = spre[0][me];
+  uint32_t a_sw;    // the address of spre[sw][me]
+  uint64_t mk, k;
+  auto set_screen = [&]() {
+    const uint32_t sw = min(best >> 3, (uint32_t)kPreW - 1), b = best - 8 * sw;
+    a_sw = a_me + sw * (uint32_t)(kN * sizeof(uint64_t));
+    k = b >= 7 ? ~0ull : (1ull << (8 * (b + 1))) - 1;
+    mk = *(LU64 *)(uintptr_t)a_sw & k;
+  };
+  set_screen();
+  bool stop = nwalk > 0 && best >= limit;
+  int tend = stop ? 0 : nwalk;   // this lane's last step (0: done)
+  // The walk ends before the first candidate beyond the window (positions ascend in a run,
+  // so distances grow with t): found up front -- by a binary search in the rare run that
+  // reaches that far -- so the steps need no distance, and read only the candidate's word.
+  if (tend > 0 && g - spos[me - nwalk] > max_dist) {
+    int lo = 0, hi = nwalk;   // d(lo) <= max_dist < d(hi)
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (g - spos[me - mid] > max_dist) hi = mid;
+      else lo = mid;
+    }
+    tend = lo;
+    stop = true;
+  }
+  GU8 *gcur = (GU8 *)(uintptr_t)cur;
+  // The exact tests of candidate t (a per-lane t): its length, capped, and its distance.
+  // Nested ifs with one way out, and no walk state written in here: the divergent part only
+  // produces the two values, the take below is selects under a wave-uniform branch (state
+  // written inside the divergent part, or an early exit from it, costs every trip of the loop
+  // around it copies of that state).
+  auto exact = [&](int t, uint32_t &len, uint32_t &d) {
+    const int e = me - t;   // (>= 0: me >= kBack)
+    d = g - spos[e];
+    const uint32_t pc = parts ? part_cap(pA, d, pbits, plag) : ~0u;   // part index: lagging source
+    if (!kParts || pc > best) {
+      static_assert(kPreW == 4, "four staged words");
+      auto first_diff = [](uint64_t x) -> uint32_t { return (uint32_t)(__ffsll((unsigned long long)x) - 1) >> 3; };
+      const uint64_t x0 = mine0 ^ spre[0][e];
+      if (x0) {
+        len = first_diff(x0);
+      } else {
+        const uint64_t x1 = spre[1][me] ^ spre[1][e];
+        if (x1) {
+          len = 8 + first_diff(x1);
+        } else {
+          const uint64_t x2 = spre[2][me] ^ spre[2][e], x3 = spre[3][me] ^ spre[3][e];
+          if (x2) {
+            len = 16 + first_diff(x2);
+          } else if (x3) {
+            len = 24 + first_diff(x3);
+          } else {
+            // measured up to the saturation length: the parse measures longer copies itself.
+            // (Past the staged bytes a candidate can only beat `best` if it matches byte `best`.)
+            len = 8 * kPreW;
+            const uint32_t lim = min(limit, kMatchLenSat);
+            if (lim > len && (best < 8 * kPreW || gcur[best] == (gcur - d)[best]))
+              len += match_len_global(gcur + len, (gcur - d) + len, lim - len);
+          }
+        }
+      }
+      len = min(min(len, limit), pc);
+    }
+  };
+  // a candidate at distance d measured to len (0: none): taken if longer than best
+  auto take = [&](uint32_t len, uint32_t d) {
+    const bool tk = len > best;
+    if (__ballot(tk) != 0) {
+      const uint32_t mt = pack_match(d, len);
+#pragma unroll
+      for (int q = 0; q + 1 < kMaxMatches; q++) stair[q] = tk ? stair[q + 1] : stair[q];
+      stair[kMaxMatches - 1] = tk ? mt : stair[kMaxMatches - 1];
+      best = tk ? len : best;
+      set_screen();   // (the same screen again for a lane that did not take)
+      // the parse measures a long copy itself; best >= limit ends the walk as well
+      const bool fin = tk & ((len >= limit) | (len >= kMatchLenSat));
+      tend = fin ? 0 : tend;
+      stop |= fin;
+    }
+  };
+  // A window of n steps from t0 (wave-uniform).  First every lane screens its n candidates with
+  // the screen it has -- no branch, the candidates at constant offsets from one address -- and
+  // keeps the passers as bits.  Then, while any lane has a bit left, each lane takes its lowest
+  // one, reads that candidate again, screens it with its screen of now, and the wave runs the
+  // exact tests for the lanes that still pass.  A candidate longer than best matches every
+  // byte up to byte best, so it passes the screen of any smaller best: a screen gone stale
+  // only lets more candidates through.  A lane takes its bits in order of t, so when a
+  // candidate meets the second screen best is what a step-by-step walk had there: the same
+  // candidates are taken in the same order.  What the windows change is how often the wave
+  // runs the exact tests: the largest number of passers any lane has in the window, not the
+  // number of steps in which some lane passes.  A lane whose walk has ended (tend = 0) drops
+  // its remaining bits.
+  auto window = [&](int t0, auto nn) {
+    constexpr int n = decltype(nn)::value;
+    // (the empty asm pins the address in its register: left to itself the compiler rebases
+    // the reads on entry me's address, below which an offset cannot be an immediate)
+    uint32_t ca = a_sw - 8u * (uint32_t)(t0 + n - 1);
+    asm volatile("" : "+v"(ca));
+    LU64 *cp = (LU64 *)(uintptr_t)ca;
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < n; j++) bits |= (cp[n - 1 - j] & k) == mk ? 1u << j : 0u;   // candidate t0 + j
+    // steps past the lane's last one (lanes past their run read another run's entry: unused)
+    const int left = tend - t0;   // steps t0 .. t0 + left are the lane's
+    bits = left < 0 ? 0u : left >= n - 1 ? bits : bits & ((2u << left) - 1);
+    while (__ballot(bits != 0) != 0) {
+      const bool has = bits != 0;
+      const int t = t0 + (__ffs(bits) - 1);   // (no bit: t0 - 1, unused)
+      bits &= bits - 1;
+      uint32_t len = 0, d = 0;
+      if (has & (t <= tend)) {
+        if ((*(LU64 *)(uintptr_t)(a_sw - 8u * (uint32_t)t) & k) == mk) exact(t, len, d);
+      }
+      take(len, d);
+    }
+  };
+  // The first step is a window of its own: with best = 3 every candidate of the bucket passes
+  // (they share the key's bytes), so step 1 runs the exact tests once for all lanes; the steps
+  // after it come in windows of kWin.
+  static_assert((kBack - 1) % kWin == 0, "step 1, then whole windows");
+  if (__ballot(1 <= tend) != 0) {
+    window(1, std::integral_constant<int, 1>{});
+    for (int tv = 2; tv <= kBack; tv += kWin) {
+      const int t0 = __builtin_amdgcn_readfirstlane(tv);
+      if (__ballot(t0 <= tend) == 0) break;
+      window(t0, std::integral_constant<int, kWin>{});
+    }
+  }
+  return stop;
 }
 
 // kHist: streaming chunks with a history table; kParts: some stream carries a part index
@@ -121,7 +329,6 @@ __global__ __launch_bounds__(kTile) void find_matches_kernel(const Job *jobs, co
   const uint32_t r = r0 + threadIdx.x;
   if (r >= total) return;
   const uint32_t key = skey[me], g = spos[me];
-  int cnt = 0;
   if ((key & kInvalidKey) == 0) {
     const uint32_t p = g - sr.pos_base;
     // (pos_base is a multiple of the segment: the segment's end in global positions)
@@ -132,163 +339,14 @@ __global__ __launch_bounds__(kTile) void find_matches_kernel(const Job *jobs, co
     const uint32_t pA = (kHist || kParts) ? jb.abs_base + p : 0u, pbits = kParts ? jb.part_bits : 16u,
                    plag = kParts ? jb.part_lag : 0u;
     uint32_t best = 3;
-    uint32_t local[kMaxMatches] = {};
-    if constexpr (!kHist) {
-      const uint64_t mine0 = spre[0][me];
-      const int dmax = min(depth, kBack), nwalk = min(dmax, nrun);
-      // The walk steps t in lockstep over the wave (a scalar loop: the run's end per lane is a
-      // compare, not a divergent exit) and screens each candidate by its first word: it needs the
-      // exact tests below iff the word's low best + 1 bytes all match (first difference past byte
-      // best, or none in the word) or it lies beyond the window.  Most candidates fail the screen,
-      // ~25 instructions each; the exact tests run under a branch the wave skips when no lane
-      // needs them.  (As one per-lane loop with break / continue every candidate paid the exit-mask
-      // bookkeeping of the rare paths, ~48 instructions, r05 ISA listing; as a per-lane skip loop
-      // the lanes' different skip lengths multiplied the steps.)  Same candidates, same order,
-      // same records.
-      auto low_bytes = [](uint32_t n) -> uint64_t { return n >= 7 ? ~0ull : (1ull << (8 * (n + 1))) - 1; };
-      uint64_t bmask = low_bytes(best);
-      int tend = best >= limit ? 0 : nwalk;   // this lane's last step (0: done)
-      // The walk ends before the first candidate beyond the window (positions ascend in a run,
-      // so distances grow with t): found up front -- by a binary search in the rare run that
-      // reaches that far -- so the steps need no distance, and read only the candidate's word.
-      if (tend > 0 && g - spos[me - nwalk] > max_dist) {
-        int lo = 0, hi = nwalk;   // d(lo) <= max_dist < d(hi)
-        while (hi - lo > 1) {
-          const int mid = (lo + hi) >> 1;
-          if (g - spos[me - mid] > max_dist) hi = mid;
-          else lo = mid;
-        }
-        tend = lo;
-      }
-      for (int t = 1; t <= kBack; t++) {
-        if (__ballot(t <= tend) == 0) break;
-        const int e = me - t;   // (>= 0: me >= kBack; lanes past their run read another run's entry, unused)
-        const uint64_t x0 = mine0 ^ spre[0][e];
-        if (!((t <= tend) & ((x0 & bmask) == 0))) continue;
-        const uint32_t d = g - spos[e];
-        const uint32_t qlen = (uint32_t)(__ffsll((unsigned long long)x0) - 1) >> 3;   // (x0 == 0: not used)
-        const uint32_t pc = parts ? part_cap(pA, d, pbits, plag) : ~0u;   // part index: lagging source
-        if (pc <= best) continue;
-        uint32_t len;
-        if (x0) {
-          len = qlen;
-        } else {
-          // a candidate can only beat `best` if it matches byte `best` too
-          if (best < 8 * kPreW) {
-            const uint32_t sh = 8 * (best & 7);
-            if (((spre[best >> 3][me] ^ spre[best >> 3][e]) >> sh) & 0xFF) continue;
-          } else if (cur[best] != (cur - d)[best]) {
-            continue;
-          }
-          len = 8 * kPreW;
-#pragma unroll
-          for (int w = 1; w < kPreW; w++) {
-            const uint64_t x = spre[w][me] ^ spre[w][e];
-            if (x) {
-              len = 8 * w + ((uint32_t)(__ffsll((unsigned long long)x) - 1) >> 3);
-              break;
-            }
-          }
-          if (len == 8 * kPreW) {
-            // measured up to the saturation length: the parse measures longer copies itself
-            const uint32_t lim = min(limit, kMatchLenSat);
-            if (lim > len) len += match_len(cur + len, (cur - d) + len, lim - len);
-          }
-        }
-        len = min(min(len, limit), pc);
-        if (len > best) {
-          best = len;
-          if (cnt == kMaxMatches) {   // keep the longest ones: drop the shortest
-            for (int q = 1; q < kMaxMatches; q++) local[q - 1] = local[q];
-            cnt--;
-          }
-          local[cnt++] = pack_match(d, len);
-          bmask = low_bytes(best);
-          // the parse measures a long copy itself; best >= limit ends the walk as well
-          if (len >= limit || len >= kMatchLenSat) tend = 0;
-        }
-      }
-      } else {
-      const uint64_t mine0 = spre[0][me];
-      // a candidate at distance d measured to len: the staircase keeps strictly longer ones;
-      // DONE: no longer candidate can matter (the parse measures a long copy itself)
-#define TAKE(d_, len_, DONE)                                               \
-    do {                                                                     \
-      const uint32_t l_ = min(min((len_), limit),                            \
-                              parts ? part_cap(pA, (d_), pbits, plag) : ~0u);   \
-      if (l_ > best) {                                                       \
-        best = l_;                                                           \
-        if (cnt == kMaxMatches) {                                            \
-          for (int q = 1; q < kMaxMatches; q++) local[q - 1] = local[q];     \
-          cnt--;                                                             \
-        }                                                                    \
-        local[cnt++] = pack_match((d_), l_);                                 \
-        if (l_ >= limit || l_ >= kMatchLenSat) DONE;                         \
-      }                                                                      \
-    } while (0)
-      const int dmax = min(depth, kBack);
-      const int nwalk = min(dmax, nrun);
-      // (the window walk as in the window-only build above: lockstep steps, the first word's
-      // screen, the window end found up front; `stop` skips the history part as the serial walk's
-      // break did -- at a candidate beyond the window, or once a copy reaches the limit)
-      auto low_bytes = [](uint32_t n) -> uint64_t { return n >= 7 ? ~0ull : (1ull << (8 * (n + 1))) - 1; };
-      uint64_t bmask = low_bytes(best);
-      bool stop = nwalk > 0 && best >= limit;
-      int tend = stop ? 0 : nwalk;
-      if (tend > 0 && g - spos[me - nwalk] > max_dist) {
-        int lo = 0, hi = nwalk;   // d(lo) <= max_dist < d(hi)
-        while (hi - lo > 1) {
-          const int mid = (lo + hi) >> 1;
-          if (g - spos[me - mid] > max_dist) hi = mid;
-          else lo = mid;
-        }
-        tend = lo;
-        stop = true;
-      }
-      for (int s = 1; s <= kBack; s++) {
-        if (__ballot(s <= tend) == 0) break;
-        const int e = me - s;
-        const uint64_t x0 = mine0 ^ spre[0][e];
-        if (!((s <= tend) & ((x0 & bmask) == 0))) continue;
-        const uint32_t d = g - spos[e];
-        const uint32_t qlen = (uint32_t)(__ffsll((unsigned long long)x0) - 1) >> 3;   // (x0 == 0: not used)
-        uint32_t len;
-        if (x0) {
-          len = qlen;
-        } else {
-          // a candidate can only beat `best` if it matches byte `best` too
-          if (best < 8 * kPreW) {
-            const uint32_t sh = 8 * (best & 7);
-            if (((spre[best >> 3][me] ^ spre[best >> 3][e]) >> sh) & 0xFF) continue;
-          } else if (cur[best] != (cur - d)[best]) {
-            continue;
-          }
-          len = 8 * kPreW;
-#pragma unroll
-          for (int w = 1; w < kPreW; w++) {
-            const uint64_t x = spre[w][me] ^ spre[w][e];
-            if (x) {
-              len = 8 * w + ((uint32_t)(__ffsll((unsigned long long)x) - 1) >> 3);
-              break;
-            }
-          }
-          if (len == 8 * kPreW) {
-            // measured up to the saturation length: the parse measures longer copies itself
-            const uint32_t lim = min(limit, kMatchLenSat);
-            if (lim > len) len += match_len(cur + len, (cur - d) + len, lim - len);
-          }
-        }
-        bool fin = false;
-        TAKE(d, len, fin = true);
-        bmask = low_bytes(best);
-        if (fin) {
-          stop = true;
-          tend = 0;
-        }
-      }
-      int t = nwalk + 1;   // (the history part's candidates count on from the window's)
-      // streaming: then the bucket's occurrences before this chunk (farther, newest first)
-      if (kHist && jb.hist_tab && !stop && t <= dmax) {
+    uint32_t local[kMaxMatches] = {};   // the staircase, right-aligned until the store
+    const int dmax = min(depth, kBack), nwalk = min(dmax, nrun);
+    const bool stop = window_walk<kParts, kTile + kBack>(spre, spos, me, nwalk, g, limit, max_dist, cur, parts, pA, pbits, plag, best, local);
+    // streaming: then the bucket's occurrences before this chunk (farther, newest first; the
+    // history part's candidates count on from the window's)
+    if constexpr (kHist) {
+      int t = nwalk + 1;
+      if (jb.hist_tab && !stop && t <= dmax) {
         const uint32_t *slot = jb.hist_tab + (size_t)(key & ((1u << kHashBits) - 1)) * kHistWays;
         const uint32_t A = jb.abs_base + p;
         const uint32_t reach = min(max_dist, p + jb.hist);
@@ -300,13 +358,16 @@ __global__ __launch_bounds__(kTile) void find_matches_kernel(const Job *jobs, co
           const uint8_t *cand = cur - d;
           if (cur[best] != cand[best]) continue;
           const uint32_t lim = min(limit, kMatchLenSat);
-          bool fin = false;
-          TAKE(d, match_len(cur, cand, lim), fin = true);
-          if (fin) break;
+          const uint32_t len = min(min(match_len(cur, cand, lim), limit), parts ? part_cap(pA, d, pbits, plag) : ~0u);
+          if (len > best) {
+            best = len;
+            stair_push(local, pack_match(d, len));
+            if (len >= limit || len >= kMatchLenSat) break;
+          }
         }
       }
-#undef TAKE
     }
+    stair_left_align(local);
     // a match word is never 0 (length >= 4): the unused tail entries mark the count
     rec_store(matches + (uint64_t)(sorted_store ? r : g) * kMatchRec, local);
     return;

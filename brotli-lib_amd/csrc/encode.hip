@@ -1183,6 +1183,92 @@ int mib_encode_batch(const mib_span *in, size_t k, const mib_enc_opts *o, mib_bu
   return encode_host(in, k, o, out, status);
 }
 
+// Diagnostic (tests): the candidate walk alone.  The batch is laid out as encode_group lays a
+// call out (every stream on its own 64 KiB-aligned range of global positions, a spare segment
+// behind it), then only the bucket sort and find_matches run -- no history table, part index,
+// near scan or dictionary pass -- and each stream's records come back stream-relative.
+int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out) {
+  if (!k || !in || !out) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++) {
+    out[i].data = nullptr;
+    out[i].size = 0;
+    if ((!in[i].data && in[i].size) || in[i].size >= (1ull << 31)) return MIB_E_INVALID_ARG;
+  }
+  DefaultLock use;
+  mib_ctx *c = mib_default_ctx();
+  if (!c) return MIB_E_NO_DEVICE;
+  CK(hipSetDevice(mib_ctx_device_of(c)));
+  hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
+  const Params prm = make_params(o);
+  std::vector<uint64_t> ioff(k + 1, 0);
+  for (size_t i = 0; i < k; i++) ioff[i + 1] = ioff[i] + ((in[i].size + 255) & ~(uint64_t)255);
+  std::vector<Job> jobs(k);
+  std::vector<uint32_t> seg_job;
+  std::vector<SegRef> seg_ref;
+  uint64_t pos_total = 0;
+  for (size_t j = 0; j < k; j++) pos_total += ((in[j].size + kSeg - 1) / kSeg) * kSeg + kSeg;
+  if (pos_total >= (1ull << 31)) return MIB_E_INVALID_ARG;
+  const uint32_t total = (uint32_t)pos_total;
+  const size_t sort_tmp = sort_ws_bytes(total);
+  size_t need = 16 * 256 + ioff[k] + 64 + 4 * (size_t)total * 4 + sort_tmp + (size_t)total * kMatchRec * 4 + k * sizeof(Job) +
+                (size_t)(total >> kSegBits) * (4 + sizeof(SegRef));
+  uint8_t *buf = nullptr;
+  if (hipMalloc(&buf, need) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
+  struct FreeAtExit {
+    uint8_t *p;
+    ~FreeAtExit() { hipFree(p); }
+  } free_at_exit{buf};
+  Arena ar{buf};
+  uint8_t *d_in = ar.take<uint8_t>(ioff[k] + 64);
+  uint32_t *keys = ar.take<uint32_t>(total), *vals = ar.take<uint32_t>(total);
+  uint32_t *skeys = ar.take<uint32_t>(total), *svals = ar.take<uint32_t>(total);
+  void *sort_ws = ar.take<uint8_t>(sort_tmp);
+  uint32_t *matches = ar.take<uint32_t>((size_t)total * kMatchRec);
+  Job *d_jobs = ar.take<Job>(k);
+  uint32_t *d_seg_job = ar.take<uint32_t>(total >> kSegBits);
+  SegRef *d_seg_ref = ar.take<SegRef>(total >> kSegBits);
+  if (ar.off > need) return MIB_E_OUT_OF_MEMORY;
+  pos_total = 0;
+  for (size_t j = 0; j < k; j++) {
+    Job &jb = jobs[j];
+    memset(&jb, 0, sizeof(jb));
+    const uint64_t n = in[j].size;
+    jb.data = d_in + ioff[j];
+    jb.n = (uint32_t)n;
+    jb.lgwin = (uint32_t)prm.lgwin;
+    jb.uncompressed = (prm.quality == 0 || n < 64) ? 1 : 0;
+    jb.font = prm.font ? 1 : 0;
+    jb.pos_base = (uint32_t)pos_total;
+    const uint64_t span = ((n + kSeg - 1) / kSeg) * kSeg + kSeg;
+    for (uint64_t q = 0; q < span / kSeg; q++) {
+      seg_job.push_back((uint32_t)j);
+      seg_ref.push_back(SegRef{jb.data - (uintptr_t)pos_total, (uint32_t)pos_total, (uint32_t)(pos_total + (jb.uncompressed ? 0 : n))});
+    }
+    pos_total += span;
+  }
+  CK(hipMemsetAsync(d_in, 0, ioff[k] + 64, st));
+  for (size_t j = 0; j < k; j++)
+    if (in[j].size) CK(hipMemcpyAsync(d_in + ioff[j], in[j].data, in[j].size, hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(d_jobs, jobs.data(), k * sizeof(Job), hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(d_seg_job, seg_job.data(), seg_job.size() * 4, hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(d_seg_ref, seg_ref.data(), seg_ref.size() * sizeof(SegRef), hipMemcpyHostToDevice, st));
+  CK(hipMemsetAsync(matches, 0, (size_t)total * kMatchRec * 4, st));
+  const int depth = (int)env_u32("MIB_DEPTH", (uint32_t)depth_for_quality(prm.quality), 1, 64);
+  launch_sort(st, d_jobs, d_seg_job, (int)k, total, hash_bytes(prm), sort_ws, keys, vals, skeys, svals);
+  launch_find_matches(st, d_jobs, d_seg_job, d_seg_ref, skeys, svals, total, depth, (1u << prm.lgwin) - 16, false, false, matches);
+  CK(hipGetLastError());
+  CK(hipStreamSynchronize(st));
+  std::vector<mib_buf *> outs(k);
+  std::vector<const uint8_t *> src(k);
+  std::vector<uint64_t> lens(k);
+  for (size_t j = 0; j < k; j++) {
+    outs[j] = &out[j];
+    src[j] = reinterpret_cast<const uint8_t *>(matches + (size_t)jobs[j].pos_base * kMatchRec);
+    lens[j] = (uint64_t)in[j].size * kMatchRec * 4;
+  }
+  return mib_bufs_from_device(k, outs.data(), src.data(), lens.data());
+}
+
 // BrotliEncoder (encode.ts:290-409): input is taken in whole blocks of 2^lgblock
 // (computeLgBlock, enc-constants.ts:129-147), at least `chunk` bytes per device encode; each
 // encode ends in a byte-aligning empty metadata block so update() returns whole bytes.  The

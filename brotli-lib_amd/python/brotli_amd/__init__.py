@@ -153,6 +153,9 @@ def _L():
                                                    ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.POINTER(_Buf)]
         lib.mib_part_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        if hasattr(lib, 'mib_debug_match_records'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_debug_match_records.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
+                                                    ctypes.POINTER(_Buf)]
         lib.mib_default_ctx.restype = ctypes.c_void_p
         lib.mib_ctx_clear_times.argtypes = [ctypes.c_void_p]
         lib.mib_set_allocator.argtypes = [_ALLOC_FN, _FREE_FN, ctypes.c_void_p]
@@ -329,6 +332,26 @@ def encode_batch(buffers, options=None, gpus=None):
     for i in range(k):
         if st[i]:
             raise _err(st[i])
+    return res
+
+
+def debug_match_records(buffers, options=None):
+    """Diagnostic (tests): the records the encoder's bucket sort and candidate walk alone give
+    a batch of buffers (mib_debug_match_records): per buffer a numpy uint32 array of shape
+    (len(buffer), entries), each entry length << 24 | distance, valid ones first, 0 after."""
+    import numpy as np
+    k = len(buffers)
+    keep = [_in(b) for b in buffers]
+    spans = (_Span * k)(*[_Span(_addr(a), n) for a, n, _ in keep])
+    outs = (_Buf * k)()
+    rc = _L().mib_debug_match_records(spans, k, ctypes.byref(_opts(options)), outs)
+    if rc:
+        raise _err(rc)
+    res = []
+    for i in range(k):
+        n = keep[i][1]
+        a = np.frombuffer(_take(outs[i]), dtype='<u4')
+        res.append(a.reshape(n, -1) if n else a.reshape(0, 4))
     return res
 
 

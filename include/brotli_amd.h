@@ -131,6 +131,13 @@ void mib_force_shards(int force);
  * finds a chosen distance in the ring), so a test can show what the candidates change; 0
  * restores them. */
 void mib_force_no_dp_cache(int off);
+/* Diagnostic (tests): the match finder's candidate walk alone.  The k host buffers are laid
+ * out as one encode call lays them out and only that call's bucket sort and find_matches run
+ * (no near scan, no dictionary passes, no history); `o` gives quality (depth), lgwin (window)
+ * and mode (key bytes).  out[i] receives stream i's records: per position MIB_MAX_MATCHES (4 in
+ * the product build) little-endian u32, each length << 24 | distance with stream-relative
+ * positions, valid entries first, longest last, zeros after. */
+int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out);
 
 void mib_buf_free(mib_buf *b);
 /* The allocator behind every mib_buf the library returns (default malloc / free), in the
