@@ -18,7 +18,12 @@
 
 #include "common.h"
 #include "parts.h"
+#include "stream_session.h"
 
+extern "C" hipError_t mib_decode_resume_launch(mib::StreamJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
+                                               int grid, int per_cu, hipStream_t stream);
+extern "C" hipError_t mib_stream_move_launch(uint8_t *d_buf, uint64_t src, uint64_t n, hipStream_t stream);
+extern "C" hipError_t mib_decode_stream_init_tables(const int16_t *host_lut);
 extern "C" hipError_t mib_decode_parts_launch(mib::DecJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
                                               unsigned *d_ticket, int grid, int per_cu, hipStream_t stream);
 extern "C" hipError_t mib_decode_launch(mib::DecJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
@@ -105,6 +110,7 @@ int ensure_device(int device) {
   int16_t lut[704 * 4];
   build_cmd_lut(lut);
   HIP_OK(mib_decode_init_tables(lut));
+  HIP_OK(mib_decode_stream_init_tables(lut));
   HIP_OK(hipDeviceSynchronize());
   const int64_t bad = mib_selftest_lds_atomic_order(4096);
   if (bad < 0) return MIB_E_NO_DEVICE;
@@ -1266,6 +1272,270 @@ int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status) {
     fprintf(stderr, "[mib] decode_batch %zu streams: upload done %.2f ms, decode done %.2f, results %.2f\n", k, t_up, t_dec,
             ms_since());
   return rc;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- streaming decoder
+// A session keeps in HBM its dictionary, the session buffer (history, a window of new output,
+// slack: stream_session.h) and the pending input (from the oldest byte a resume reads again),
+// and between launches the checkpoint.  update() appends its bytes to the pending input and
+// launches decode_resume_kernel until a launch suspends for input; a launch that stops on the
+// output limit has its bytes copied out and the history moved to the buffer's front first.
+struct mib_decoder {
+  int64_t max_out = -1;
+  uint64_t out_window = 0;
+  std::vector<uint8_t> dict;          // customDictionary until the device copy exists
+  bool has_dict = false;
+  uint8_t *d_dict = nullptr, *d_buf = nullptr, *d_in = nullptr, *d_scratch = nullptr;
+  uint64_t buf_cap = 0, in_cap = 0, in_len = 0;
+  mib::StreamCkpt *d_ck = nullptr;
+  mib::StreamJob *d_job = nullptr;
+  mib::StreamCkpt ck;                 // host mirror (its window stays on the device)
+  int lgwin = 0;                      // 0: the stream's first byte has not arrived
+  uint64_t total_out = 0, passes = 0, redone = 0;   // redone: output bytes decoded twice (behind a checkpoint)
+  uint64_t need_len = 0;              // pending bytes the next launch needs at least (0: unknown)
+  int error = 0;
+  bool finished = false;
+  int device = 0;
+};
+
+namespace {
+int g_force_small_decoder = 0;   // mib_force_decoder_build
+constexpr size_t kCkHead = offsetof(mib::StreamCkpt, win);
+constexpr uint64_t kStreamScratch =
+    (mib::kDecodeTableInts * 4 + mib::kDecodeCtxBytes + 1152 + 1152 * 4 + 1100 * 4 + 3092 * 4 + 255) & ~(uint64_t)255;
+
+void decoder_release(mib_decoder *d) {
+  hipSetDevice(d->device);
+  for (void *p : {(void *)d->d_dict, (void *)d->d_buf, (void *)d->d_in, (void *)d->d_scratch, (void *)d->d_ck, (void *)d->d_job})
+    if (p) hipFree(p);
+  d->d_dict = d->d_buf = d->d_in = d->d_scratch = nullptr;
+  d->d_ck = nullptr;
+  d->d_job = nullptr;
+  d->buf_cap = d->in_cap = d->in_len = 0;
+}
+
+// the stream's first byte is here: its window sizes the session buffer
+int decoder_open(mib_decoder *d, mib_ctx *c, uint8_t first) {
+  const int lgwin = mib::stream_window_bits(first);
+  if (lgwin < 0) return -11;   // the reserved window-bits pattern (engine.ts decodeWindowBits)
+  d->lgwin = lgwin;
+  d->buf_cap = mib::stream_buf_cap(lgwin, d->out_window);
+  if (hipMalloc((void **)&d->d_buf, d->buf_cap) != hipSuccess || hipMalloc((void **)&d->d_scratch, kStreamScratch) != hipSuccess ||
+      hipMalloc((void **)&d->d_ck, sizeof(mib::StreamCkpt)) != hipSuccess || hipMalloc((void **)&d->d_job, sizeof(mib::StreamJob)) != hipSuccess)
+    return MIB_E_OUT_OF_MEMORY;
+  if (d->has_dict) {
+    if (hipMalloc((void **)&d->d_dict, d->dict.size() + 16) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
+    const mib::HostPiece up{d->d_dict, d->dict.data(), d->dict.size()};
+    int rc = mib::ctx_upload(c, c->stream, &up, 1);
+    if (rc) return rc;
+  }
+  mib::stream_initial_ckpt(&d->ck, lgwin);
+  HIP_OK(hipMemcpyAsync(d->d_ck, &d->ck, sizeof(d->ck), hipMemcpyHostToDevice, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));   // (d->ck / d->dict are read by the copies)
+  return 0;
+}
+
+int decoder_append(mib_decoder *d, mib_ctx *c, const uint8_t *in, size_t n) {
+  if (d->in_len + n + 16 > d->in_cap) {
+    const uint64_t cap = std::max<uint64_t>(2 * d->in_cap, std::max<uint64_t>(d->in_len + n + 16, 1 << 16));
+    uint8_t *p = nullptr;
+    if (hipMalloc((void **)&p, cap) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
+    if (d->in_len) {
+      if (hipMemcpyAsync(p, d->d_in, d->in_len, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+          hipStreamSynchronize(c->stream) != hipSuccess) {
+        hipFree(p);
+        return MIB_E_NO_DEVICE;
+      }
+    }
+    if (d->d_in) hipFree(d->d_in);
+    d->d_in = p;
+    d->in_cap = cap;
+  }
+  if (n) {
+    const mib::HostPiece up{d->d_in + d->in_len, in, n};
+    int rc = mib::ctx_upload(c, c->stream, &up, 1);
+    if (rc) return rc;
+    d->in_len += n;
+  }
+  return 0;
+}
+
+int decoder_put_ckpt(mib_decoder *d, mib_ctx *c) {
+  HIP_OK(hipMemcpyAsync(d->d_ck, &d->ck, kCkHead, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// launches until one suspends for input, the stream ends or fails; the bytes decoded go to `got`
+int decoder_run(mib_decoder *d, mib_ctx *c, int final, std::vector<uint8_t> &got) {
+  // the last launch stopped in front of a raw or metadata block that is still not whole
+  if (!final && d->in_len < d->need_len) return 0;
+  for (;;) {
+    // the history to the buffer's front: the next launch needs out_window + slack behind pos
+    const uint64_t delta = mib::stream_compact_delta(d->ck.e.pos, d->lgwin);
+    if (delta) {
+      HIP_OK(mib_stream_move_launch(d->d_buf, delta, d->ck.e.pos - delta, c->stream));
+      mib::stream_rebase_output(&d->ck, delta);
+      int rc = decoder_put_ckpt(d, c);
+      if (rc) return rc;
+    }
+    const uint64_t start = d->ck.e.pos;
+    mib::StreamJob j;
+    memset(&j, 0, sizeof(j));
+    j.in = d->d_in;
+    j.in_len = d->in_len;
+    j.buf = d->d_buf;
+    j.buf_cap = d->buf_cap;
+    j.out_limit = start + d->out_window;
+    j.dict = d->d_dict;
+    j.dict_len = d->has_dict ? d->dict.size() : 0;
+    j.ck = d->d_ck;
+    j.lgwin = d->lgwin;
+    j.final = final;
+    HIP_OK(hipMemcpyAsync(d->d_job, &j, sizeof(j), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(mib_decode_resume_launch(d->d_job, 1, d->d_scratch, kStreamScratch, 1,
+                                    __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, 1), c->stream));
+    HIP_OK(hipMemcpyAsync(&j, d->d_job, sizeof(j), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(&d->ck, d->d_ck, kCkHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    d->passes++;
+    if (j.status == mib::kStreamNeedInput && j.redone > 0) d->redone += (uint64_t)j.redone;
+    if (j.status < 0) return j.status;
+    if (j.out_pos < (int64_t)start || (uint64_t)j.out_pos > d->buf_cap) return MIB_E_NO_PROGRESS;
+    const uint64_t n = (uint64_t)j.out_pos - start;
+    d->total_out += n;
+    if (d->max_out >= 0 && d->total_out > (uint64_t)d->max_out) return MIB_E_OUTPUT_LIMIT;
+    if (n) {
+      const size_t at = got.size();
+      got.resize(at + n);
+      const mib::HostPiece down{got.data() + at, d->d_buf + start, n};
+      int rc = mib::ctx_download(c, c->stream, &down, 1);
+      if (rc) return rc;
+    }
+    if (j.status == mib::kStreamFinished) {
+      d->finished = true;
+      // bytes behind the stream's end: refused, as one-shot decoding refuses them (-17)
+      return d->in_len > ((d->ck.e.bit + 7) >> 3) ? -17 : 0;
+    }
+    if (j.status == mib::kStreamNeedOutput) continue;   // (the checkpoint is where the launch left)
+    if (j.status != mib::kStreamNeedInput || final) return MIB_E_NO_PROGRESS;
+    d->need_len = j.need_len > 0 ? (uint64_t)j.need_len : 0;
+    break;
+  }
+  // input no resume reads again leaves the front of the pending bytes (once it is worth a move)
+  const uint64_t keep = mib::stream_keep_from(d->ck);
+  if (keep >= (64u << 10) && 2 * keep >= d->in_len) {
+    HIP_OK(mib_stream_move_launch(d->d_in, keep, d->in_len - keep, c->stream));
+    d->in_len -= keep;
+    d->need_len = d->need_len > keep ? d->need_len - keep : 0;
+    mib::stream_rebase_input(&d->ck, keep);
+    int rc = decoder_put_ckpt(d, c);
+    if (rc) return rc;
+    HIP_OK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+
+int decoder_result(mib_decoder *d, int rc, std::vector<uint8_t> &got, mib_buf *out) {
+  if (rc == 0) {
+    out->data = mib_buf_alloc(got.size());
+    if (!out->data) rc = MIB_E_OUT_OF_MEMORY;
+    else {
+      out->size = got.size();
+      if (!got.empty()) memcpy(out->data, got.data(), got.size());
+    }
+  }
+  if (rc) {
+    d->error = rc;   // every later call reports it; the device memory goes now
+    if (rc == MIB_E_OUTPUT_LIMIT) out->size = (size_t)d->total_out;
+    decoder_release(d);
+  }
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+void mib_dec_opts_default(mib_dec_opts *o) {
+  if (!o) return;
+  o->dict = nullptr;
+  o->dict_len = 0;
+  o->max_out = -1;
+  o->out_window = 0;
+}
+
+mib_decoder *mib_decoder_new(const mib_dec_opts *o) {
+  mib_dec_opts def;
+  mib_dec_opts_default(&def);
+  if (!o) o = &def;
+  if ((!o->dict && o->dict_len) || o->max_out < -1) return nullptr;
+  mib_decoder *d = new mib_decoder();
+  d->max_out = o->max_out;
+  d->out_window = mib::stream_clamp_window(o->out_window);
+  if (o->dict) {   // (an empty dictionary is still attached, as in brotliDecode)
+    d->has_dict = true;
+    d->dict.assign(o->dict, o->dict + o->dict_len);
+  }
+  return d;
+}
+
+int mib_decoder_update(mib_decoder *d, const uint8_t *in, size_t n, mib_buf *out) {
+  if (!d || !out || (!in && n)) return MIB_E_INVALID_ARG;
+  out->data = nullptr;
+  out->size = 0;
+  if (d->error) return d->error;
+  std::vector<uint8_t> got;
+  if (n == 0) return decoder_result(d, 0, got, out);
+  if (d->finished) return decoder_result(d, -17, got, out);
+  DefaultUse use;
+  mib_ctx *c = default_ctx();
+  if (!c) return MIB_E_NO_DEVICE;
+  hipSetDevice(c->device);
+  d->device = c->device;
+  int rc = 0;
+  if (!d->lgwin) rc = decoder_open(d, c, in[0]);
+  if (!rc) rc = decoder_append(d, c, in, n);
+  if (!rc) rc = decoder_run(d, c, 0, got);
+  return decoder_result(d, rc, got, out);
+}
+
+int mib_decoder_finish(mib_decoder *d, mib_buf *out) {
+  if (!d || !out) return MIB_E_INVALID_ARG;
+  out->data = nullptr;
+  out->size = 0;
+  if (d->error) return d->error;
+  std::vector<uint8_t> got;
+  if (d->finished) return decoder_result(d, 0, got, out);
+  DefaultUse use;
+  mib_ctx *c = default_ctx();
+  if (!c) return MIB_E_NO_DEVICE;
+  hipSetDevice(c->device);
+  d->device = c->device;
+  int rc = 0;
+  // no byte at all: the decoder reads an empty input's padding, window bits 0 (16) first
+  if (!d->lgwin) rc = decoder_open(d, c, 0);
+  if (!rc) rc = decoder_append(d, c, nullptr, 0);
+  if (!rc) rc = decoder_run(d, c, 1, got);
+  return decoder_result(d, rc, got, out);
+}
+
+int mib_decoder_is_finished(const mib_decoder *d) { return d && d->finished && !d->error; }
+
+void mib_decoder_stats(const mib_decoder *d, uint64_t *passes, uint64_t *redecoded) {
+  if (passes) *passes = d ? d->passes : 0;
+  if (redecoded) *redecoded = d ? d->redone : 0;
+}
+
+void mib_force_decoder_build(int four_per_cu) { __atomic_store_n(&g_force_small_decoder, four_per_cu ? 1 : 0, __ATOMIC_RELAXED); }
+
+void mib_decoder_free(mib_decoder *d) {
+  if (!d) return;
+  if (d->d_buf || d->d_in || d->d_dict) {
+    DefaultUse use;
+    decoder_release(d);
+  }
+  delete d;
 }
 
 }  // extern "C"

@@ -213,6 +213,91 @@ static napi_value js_encoder_finish(napi_env env, napi_callback_info info) {
   return take(env, &b);
 }
 
+static void decoder_finalize(napi_env env, void *data, void *hint) {
+  (void)env;
+  (void)hint;
+  mib_decoder_free((mib_decoder *)data);
+}
+
+static napi_value throw_decoder(napi_env env, int rc, mib_buf *b) {
+  if (rc == MIB_E_OUTPUT_LIMIT) {   /* as js_decode: index.js rewrites the message */
+    napi_value err, msg, sz;
+    napi_create_string_utf8(env, "Decompressed size exceeds limit", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_create_int64(env, (int64_t)b->size, &sz);
+    napi_set_named_property(env, err, "size", sz);
+    napi_throw(env, err);
+    return NULL;
+  }
+  return throw_code(env, rc);
+}
+
+/* decoderNew(dictionary|null, maxOutputSize|-1, outWindow|0) -> external handle (the decoder
+ * copies the dictionary) */
+static napi_value js_decoder_new(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  mib_dec_opts o;
+  mib_dec_opts_default(&o);
+  size_t dn = 0;
+  if (argc > 0 && get_bytes(env, argv[0], &o.dict, &dn) == 0) o.dict_len = dn;
+  else o.dict = NULL;
+  const int64_t mo = argc > 1 ? get_i64(env, argv[1], -1) : -1;
+  o.max_out = mo < 0 ? -1 : mo;
+  const int64_t ow = argc > 2 ? get_i64(env, argv[2], 0) : 0;
+  o.out_window = ow > 0 ? (uint64_t)ow : 0;
+  mib_decoder *d = mib_decoder_new(&o);
+  if (!d) return throw_code(env, MIB_E_OUT_OF_MEMORY);
+  CHECK(env, napi_create_external(env, d, decoder_finalize, NULL, &out));
+  return out;
+}
+
+static napi_value js_decoder_update(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void *h;
+  const uint8_t *p;
+  size_t n;
+  if (argc < 2 || napi_get_value_external(env, argv[0], &h) != napi_ok || get_bytes(env, argv[1], &p, &n)) {
+    napi_throw_type_error(env, NULL, "update(chunk: Uint8Array)");
+    return NULL;
+  }
+  mib_buf b = {0, 0};
+  int rc = mib_decoder_update((mib_decoder *)h, p, n, &b);
+  if (rc) return throw_decoder(env, rc, &b);
+  return take(env, &b);
+}
+
+static napi_value js_decoder_finish(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void *h;
+  if (argc < 1 || napi_get_value_external(env, argv[0], &h) != napi_ok) {
+    napi_throw_type_error(env, NULL, "finish()");
+    return NULL;
+  }
+  mib_buf b = {0, 0};
+  int rc = mib_decoder_finish((mib_decoder *)h, &b);
+  if (rc) return throw_decoder(env, rc, &b);
+  return take(env, &b);
+}
+
+static napi_value js_decoder_finished(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void *h;
+  if (argc < 1 || napi_get_value_external(env, argv[0], &h) != napi_ok) {
+    napi_throw_type_error(env, NULL, "finished");
+    return NULL;
+  }
+  CHECK(env, napi_get_boolean(env, mib_decoder_is_finished((const mib_decoder *)h) != 0, &out));
+  return out;
+}
+
 /* encodeBatch([bytes...], quality, lgwin, mode, gpus, dictionary|null) -> [Buffer...]: one GPU
  * launch sequence (gpus >= 0: sharded over that many GPUs, 0 = all; -1 / absent: the default
  * device) */
@@ -489,6 +574,10 @@ static napi_value init(napi_env env, napi_value exports) {
       {"encoderNew", 0, js_encoder_new, 0, 0, 0, napi_default, 0},
       {"encoderUpdate", 0, js_encoder_update, 0, 0, 0, napi_default, 0},
       {"encoderFinish", 0, js_encoder_finish, 0, 0, 0, napi_default, 0},
+      {"decoderNew", 0, js_decoder_new, 0, 0, 0, napi_default, 0},
+      {"decoderUpdate", 0, js_decoder_update, 0, 0, 0, napi_default, 0},
+      {"decoderFinish", 0, js_decoder_finish, 0, 0, 0, napi_default, 0},
+      {"decoderFinished", 0, js_decoder_finished, 0, 0, 0, napi_default, 0},
       {"encodeBatch", 0, js_encode_batch, 0, 0, 0, napi_default, 0},
       {"encodeBatchAsync", 0, js_encode_batch_async, 0, 0, 0, napi_default, 0},
       {"decodeBatchAsync", 0, js_decode_batch_async, 0, 0, 0, napi_default, 0},

@@ -40,6 +40,29 @@ export interface BrotliDecodeOptions {
 /** options as a number: the legacy exact output size (truncate / zero-pad) */
 export declare function brotliDecode(buffer: Uint8Array, options?: BrotliDecodeOptions | number): Uint8Array
 
+export interface BrotliDecoderOptions {
+  /** limit on the total output; passing it throws "Decompressed size X exceeds limit Y" */
+  maxOutputSize?: number
+  /** compound dictionary (engine.ts:142-159), copied by the decoder */
+  customDictionary?: Uint8Array | Int8Array
+  /** output bytes per device pass, default 16 MiB, clamped to 64 KiB .. 512 MiB */
+  outWindow?: number
+}
+
+/** extension (the reference decodes in one shot only): the decode side of BrotliEncoder. The
+ *  last 2^lgwin bytes of output, the input still needed and the decoder's state stay on the GPU
+ *  between calls, so a stream of any length decodes as it arrives. Bytes behind the stream's end
+ *  throw "Brotli error code: -17"; after an error every call throws it again. */
+export declare class BrotliDecoder {
+  constructor(options?: BrotliDecoderOptions)
+  /** the next bytes of the stream, cut anywhere; returns the bytes they complete (may be empty) */
+  update(chunk: Uint8Array): Uint8Array
+  /** the input has ended: the remaining bytes, or the decoder's error for an incomplete stream */
+  finish(): Uint8Array
+  /** the stream's last metablock has been decoded */
+  readonly finished: boolean
+}
+
 /** decoded size from the first metablock header, -1 when unknown */
 export declare function brotliDecodedSize(buffer: Uint8Array): number
 

@@ -6,6 +6,8 @@
 //   brotliDecode(data, {maxOutputSize, customDictionary} | outputSize)
 //                                                            src/decode/decode.ts:18-65
 //   brotliDecodedSize(data)                                  src/decode/decode.ts:9-11
+//   new BrotliDecoder(options).update(chunk) / .finish() / .finished
+//                                                            extension: streaming decode
 //   EncoderMode                                              src/encode/enc-constants.ts:56-60
 // The addon (brotli_amd.node) is built by __graft_entry__.build(); there is no JavaScript
 // fallback, a missing GPU throws.
@@ -79,6 +81,38 @@ function brotliDecode(buffer, options) {
   }
 }
 
+// BrotliDecoder (extension: the reference decodes in one shot only): the decode side of
+// BrotliEncoder.  update(chunk) takes the next bytes of one stream, cut anywhere, and returns
+// the bytes they complete; finish() declares the input ended and returns the rest, or throws
+// the decoder's error for an incomplete stream; finished: the last metablock is decoded.
+// options: customDictionary, maxOutputSize (total), outWindow (output bytes per device pass).
+class BrotliDecoder {
+  constructor(options) {
+    const o = options || {}
+    const d = o.customDictionary
+    const dict = d ? (d instanceof Uint8Array ? d : new Uint8Array(d.buffer, d.byteOffset, d.byteLength)) : null
+    this._max = o.maxOutputSize
+    this._h = native.decoderNew(dict, o.maxOutputSize === undefined ? -1 : o.maxOutputSize, o.outWindow ? Math.max(0, o.outWindow) : 0)
+  }
+  _call(f, ...args) {
+    try {
+      return toU8(f(this._h, ...args))
+    } catch (e) {
+      if (e && e.size !== undefined) throw new Error(`Decompressed size ${e.size} exceeds limit ${this._max}`)
+      throw e
+    }
+  }
+  update(input) {
+    return this._call(native.decoderUpdate, input)
+  }
+  finish() {
+    return this._call(native.decoderFinish)
+  }
+  get finished() {
+    return native.decoderFinished(this._h)
+  }
+}
+
 // options.gpus: shard the batch over that many GPUs (0: every visible one); absent: one GPU
 function gpusOf(options) {
   const g = options && options.gpus
@@ -121,7 +155,7 @@ function woff2ReconstructHmtx(data, glyf, loca, numGlyphs, numHMetrics) {
 }
 
 module.exports = {
-  brotliEncode, BrotliEncoder, brotliDecode, brotliDecodedSize, EncoderMode,
+  brotliEncode, BrotliEncoder, brotliDecode, BrotliDecoder, brotliDecodedSize, EncoderMode,
   brotliEncodeBatch, brotliEncodeBatchAsync, brotliDecodeBatchAsync,
   woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx,
 }

@@ -3,6 +3,7 @@
     brotliEncode(input, options)   src/encode/encode.ts:50-90
     BrotliEncoder(options)         src/encode/encode.ts:290-490
     brotliDecode(data, options)    src/decode/decode.ts:18-65   (options dict or legacy int)
+    BrotliDecoder(options)         extension: the streaming decode side of BrotliEncoder
     brotliDecodedSize(data)        src/decode/decode.ts:9-11
     EncoderMode                    src/encode/enc-constants.ts:56-60
 
@@ -15,7 +16,7 @@ fallback -- without an MI355X the calls raise.
 import ctypes
 import os
 
-__all__ = ['brotliEncode', 'BrotliEncoder', 'brotliDecode', 'brotliDecodedSize', 'EncoderMode', 'BrotliError',
+__all__ = ['brotliEncode', 'BrotliEncoder', 'brotliDecode', 'BrotliDecoder', 'brotliDecodedSize', 'EncoderMode', 'BrotliError',
            'encode_batch', 'decode_batch', 'encoder_update_batch', 'DeviceContext', 'library_path']
 
 _PKG = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,6 +44,11 @@ class _Opts(ctypes.Structure):
     _fields_ = [('quality', ctypes.c_int), ('lgwin', ctypes.c_int), ('mode', ctypes.c_int),
                 ('size_hint', ctypes.c_uint64), ('dict', ctypes.c_char_p), ('dict_len', ctypes.c_uint64),
                 ('stream_chunk', ctypes.c_uint64)]
+
+
+class _DecOpts(ctypes.Structure):
+    _fields_ = [('dict', ctypes.c_char_p), ('dict_len', ctypes.c_uint64), ('max_out', ctypes.c_int64),
+                ('out_window', ctypes.c_uint64)]
 
 
 class _Buf(ctypes.Structure):
@@ -126,6 +132,17 @@ def _L():
         lib.mib_encoder_free.argtypes = [ctypes.c_void_p]
         lib.mib_encoder_update_batch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_Span), ctypes.c_size_t,
                                                  ctypes.POINTER(_Buf)]
+        if hasattr(lib, 'mib_decoder_new'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_decoder_new.argtypes = [ctypes.POINTER(_DecOpts)]
+            lib.mib_decoder_new.restype = ctypes.c_void_p
+            lib.mib_decoder_update.argtypes = [ctypes.c_void_p, u8p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
+            lib.mib_decoder_finish.argtypes = [ctypes.c_void_p, ctypes.POINTER(_Buf)]
+            lib.mib_decoder_is_finished.argtypes = [ctypes.c_void_p]
+            lib.mib_decoder_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+            lib.mib_decoder_stats.restype = None
+            lib.mib_force_decoder_build.argtypes = [ctypes.c_int]
+            lib.mib_force_decoder_build.restype = None
+            lib.mib_decoder_free.argtypes = [ctypes.c_void_p]
         lib.mib_encode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
                                          ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_decode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Buf),
@@ -312,6 +329,71 @@ def brotliDecode(buffer, options=None):
     if rc:
         raise _err(rc)
     return _take(buf)
+
+
+class BrotliDecoder:
+    """Streaming decoder (extension: the reference decodes in one shot only).  update(chunk)
+    takes the next bytes of one stream, cut anywhere, and returns the bytes they complete;
+    finish() declares the input ended and returns the rest, raising the reference decoder's
+    error for an incomplete stream; `finished` is true once the last metablock is decoded.
+    options: {'customDictionary', 'maxOutputSize' (total), 'outWindow' (output bytes per device
+    pass, default 16 MiB, 64 KiB .. 512 MiB)}.  Bytes behind the stream's end raise code -17;
+    after an error every call raises it again."""
+
+    def __init__(self, options=None):
+        options = options or {}
+        o = _DecOpts(None, 0, -1, 0)
+        if options.get('customDictionary') is not None:
+            d = _bytes(options['customDictionary'])
+            o.dict, o.dict_len = d, len(d)
+        if options.get('maxOutputSize') is not None:
+            o.max_out = max(0, int(options['maxOutputSize']))
+        if options.get('outWindow') is not None:
+            o.out_window = max(0, int(options['outWindow']))
+        self._max_out = o.max_out
+        self._h = _L().mib_decoder_new(ctypes.byref(o))
+        if not self._h:
+            raise BrotliError('brotli_amd: decoder creation failed')
+
+    def _result(self, rc, buf):
+        if rc == -103:
+            raise BrotliError('Decompressed size %d exceeds limit %d' % (buf.size, self._max_out), rc)
+        if rc:
+            raise _err(rc)
+        return _take(buf)
+
+    def update(self, chunk):
+        data, n, _keep = _in(chunk)
+        buf = _Buf()
+        return self._result(_L().mib_decoder_update(self._h, data, n, ctypes.byref(buf)), buf)
+
+    def finish(self):
+        buf = _Buf()
+        return self._result(_L().mib_decoder_finish(self._h, ctypes.byref(buf)), buf)
+
+    @property
+    def finished(self):
+        return bool(_L().mib_decoder_is_finished(self._h))
+
+    def _stats(self):
+        p, r = ctypes.c_uint64(), ctypes.c_uint64()
+        _L().mib_decoder_stats(self._h, ctypes.byref(p), ctypes.byref(r))
+        return int(p.value), int(r.value)
+
+    @property
+    def passes(self):
+        """diagnostic (tests): device passes made so far"""
+        return self._stats()[0]
+
+    @property
+    def redecoded(self):
+        """diagnostic: output bytes decoded more than once so far"""
+        return self._stats()[1]
+
+    def __del__(self):
+        if getattr(self, '_h', None):
+            _L().mib_decoder_free(self._h)
+            self._h = None
 
 
 def encode_batch(buffers, options=None, gpus=None):

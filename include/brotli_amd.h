@@ -9,12 +9,13 @@
  *   brotliDecode(data, {maxOutputSize, customDictionary} | outputSize)
  *                                                          src/decode/decode.ts:13-65        -> mib_decode
  *   brotliDecodedSize(data)                                src/decode/decode.ts:9-11         -> mib_decoded_size
+ *   new BrotliDecoder(opts).update(chunk) / .finish()      (extension: streaming decode)     -> mib_decoder_*
  *   EncoderMode {GENERIC 0, TEXT 1, FONT 2}                src/encode/enc-constants.ts:56-60 -> MIB_MODE_*
  *
  * plus batch entry points (host or device-resident buffers) that shard independent buffers
  * over the GPU.  Every call is synchronous.  The host-buffer entry points
  * share one default context and are serialised internally (safe from several threads); a
- * mib_ctx / mib_encoder handle must not be used by two threads at once.
+ * mib_ctx / mib_encoder / mib_decoder handle must not be used by two threads at once.
  * All compute runs on the GPU: there is no CPU fallback, a missing device is an error.
  *
  * Return codes: 0 = success; the reference decoder's own negative codes (-1..-30,
@@ -102,6 +103,45 @@ void mib_encoder_free(mib_encoder *e);
 /* k independent encoders (distinct handles) advance by one chunk each in one launch sequence
  * (encoders with equal options share it); out[i] is encoder i's update() result. */
 int mib_encoder_update_batch(mib_encoder *const *e, const mib_span *in, size_t k, mib_buf *out);
+
+/* BrotliDecoder (extension: the reference decodes in one shot only, decode.ts:18-65; this is
+ * the decode side of BrotliEncoder, in the shape of Node's zlib.BrotliDecompress and of
+ * google/brotli's BrotliDecoderDecompressStream).  update() takes the next bytes of one
+ * stream, cut anywhere, and returns the bytes they complete (the last few KiB of them may
+ * come with the next call; the update() that brings the stream's last byte returns all that
+ * is left); finish() declares the input ended and returns the rest, or the reference
+ * decoder's error for an incomplete stream (-13, -16, -17 ...).  The decoder keeps the last 2^lgwin bytes of output, the input it may read
+ * again and its state at the last command boundary in HBM, so neither the
+ * compressed nor the decoded stream is ever held whole and its length has no limit.
+ * Bytes behind the stream's end are an error (-17), in the update() that brings them or in
+ * any later one; after an error every call returns that code again.  Output is that of
+ * brotliDecode without a size (no truncation or padding to a header's size).
+ *   dict / dict_len  customDictionary (host memory, copied by mib_decoder_new); NULL: none
+ *   max_out          limit on the total output, -1 none: MIB_E_OUTPUT_LIMIT once passed
+ *                    (no data; out->size holds the total decoded by then)
+ *   out_window       output bytes per device pass, 0 = default (16 MiB); clamped to
+ *                    64 KiB .. 512 MiB.  Smaller: less memory, more passes. */
+typedef struct {
+  const uint8_t *dict;
+  uint64_t dict_len;
+  int64_t max_out;
+  uint64_t out_window;
+} mib_dec_opts;
+void mib_dec_opts_default(mib_dec_opts *o);   /* no dictionary, max_out -1, out_window 0 */
+typedef struct mib_decoder mib_decoder;
+mib_decoder *mib_decoder_new(const mib_dec_opts *o);   /* o NULL: the defaults */
+int mib_decoder_update(mib_decoder *d, const uint8_t *in, size_t n, mib_buf *out);
+int mib_decoder_finish(mib_decoder *d, mib_buf *out);
+int mib_decoder_is_finished(const mib_decoder *d);   /* the last metablock has been decoded */
+void mib_decoder_free(mib_decoder *d);
+/* Diagnostic (tests, scripts/stream_decode_rate.py): device passes (decode launches) the
+ * session has made, and the output bytes it decoded more than once (a launch that runs out of
+ * input goes back to its last checkpoint).  Either pointer may be NULL. */
+void mib_decoder_stats(const mib_decoder *d, uint64_t *passes, uint64_t *redecoded);
+/* Diagnostic (tests): a lone session runs the decode kernel's one-stream-per-CU build (65,536
+ * LDS table entries); non-zero makes every session launch the four-per-CU build instead (12,224
+ * entries, block-type trees in scratch), the one a batch of sessions would get; 0 restores. */
+void mib_force_decoder_build(int four_per_cu);
 
 /* Batches of independent buffers in host memory; one result (and status) per buffer. */
 int mib_encode_batch(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out, int *status);
