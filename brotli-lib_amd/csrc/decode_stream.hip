@@ -10,6 +10,7 @@
 // are, instruction for instruction, what they were.
 #define MIB_TU_VAR static
 #include "decode_core.inc"
+#include "stream_batch.h"
 
 namespace mib {
 
@@ -110,7 +111,8 @@ __device__ int stream_run(DecS &s, const StreamJob &job, StreamCtl *c, int8_t *d
 }
 
 template <bool BIG>
-__global__ __launch_bounds__(64) void decode_resume_kernel(StreamJob *jobs, int njobs, uint8_t *scratch, uint64_t per_block) {
+__global__ __launch_bounds__(64) void decode_resume_kernel(StreamJob *jobs, int njobs, uint8_t *scratch, uint64_t per_block,
+                                                               uint8_t *heads) {
   constexpr int tab_cap = BIG ? kLdsTabBig : kLdsTab;
   __shared__ uint16_t tab[tab_cap];
   __shared__ int32_t bt_lds[BIG ? kBlockTreesCap + 1 : 1];
@@ -124,6 +126,14 @@ __global__ __launch_bounds__(64) void decode_resume_kernel(StreamJob *jobs, int 
   int32_t *block_trees = BIG ? bt_lds : ctxmap_table + 1100;
   for (int jb = blockIdx.x; jb < njobs; jb += gridDim.x) {
     const StreamJob job = jobs[jb];
+    // A batch launch (heads != null) carries the checkpoint heads beside its jobs, so the host
+    // sends and fetches them in one copy each: the head goes to the session's checkpoint here
+    // and comes back below.  The block's waves share one CU, so the barrier orders the stores.
+    uint64_t *slot = heads ? reinterpret_cast<uint64_t *>(heads + (uint64_t)jb * kStreamCkHead) : nullptr;
+    if (slot) {
+      if (LANE < (int)(kStreamCkHead / 8)) reinterpret_cast<uint64_t *>(job.ck)[LANE] = slot[LANE];
+      __syncthreads();
+    }
     DecJob dj;
     dj.in = job.in;
     dj.in_len = job.in_len;
@@ -144,48 +154,126 @@ __global__ __launch_bounds__(64) void decode_resume_kernel(StreamJob *jobs, int 
       jobs[jb].out_pos = status == kStreamFinished ? (int64_t)s.pos : status > 0 ? (int64_t)ctl.pos : 0;
     }
     __syncthreads();
+    if (slot && LANE < (int)(kStreamCkHead / 8)) slot[LANE] = reinterpret_cast<const uint64_t *>(job.ck)[LANE];
   }
 }
 
-// buf[0, n) <- buf[src, src + n), src > 0: the session's history moves to the front of its
-// buffer (or its pending input to the front of its).  The ranges may overlap.  A block takes
-// tile after tile, each loaded whole before it is stored, so a tile's stores (below its own
-// sources, src > 0) cannot reach what a LATER tile of the same block still has to read; with
-// overlap the host launches one block, which then owns every tile in ascending order.
-// Without overlap (src >= n) any grid is safe: no store lands in the source range.
-constexpr int kMoveThreads = 1024;
-__global__ __launch_bounds__(kMoveThreads) void stream_move_kernel(uint8_t *buf, uint64_t src, uint64_t n) {
-  constexpr uint64_t kTile = (uint64_t)kMoveThreads * 16;
-  for (uint64_t t0 = (uint64_t)blockIdx.x * kTile; t0 < n; t0 += (uint64_t)gridDim.x * kTile) {
-    uint8_t v[16];
-    const uint64_t a = t0 + (uint64_t)threadIdx.x * 16;
+// ---------------------------------------------------------------- moves and gathers (stream_batch.h)
+// 16 source bytes of any alignment: the two aligned vectors they lie in, shifted together.
+// Only called for 16 bytes that all belong to the source, so the second vector (read when the
+// address is not aligned) holds the last of them and lies in the same allocation.
+__device__ __forceinline__ uint4 load16_any(const uint8_t *s) {
+  const uint32_t sh = (uint32_t)((uintptr_t)s & 15);
+  const uint4 *p = reinterpret_cast<const uint4 *>(s - sh);
+  const uint4 lo = p[0];
+  if (sh == 0) return lo;
+  const uint4 hi = p[1];
+  uint32_t w0, w1, w2, w3, w4;
+  switch (sh >> 2) {
+    case 0: w0 = lo.x; w1 = lo.y; w2 = lo.z; w3 = lo.w; w4 = hi.x; break;
+    case 1: w0 = lo.y; w1 = lo.z; w2 = lo.w; w3 = hi.x; w4 = hi.y; break;
+    case 2: w0 = lo.z; w1 = lo.w; w2 = hi.x; w3 = hi.y; w4 = hi.z; break;
+    default: w0 = lo.w; w1 = hi.x; w2 = hi.y; w3 = hi.z; w4 = hi.w; break;
+  }
+  const uint32_t bs = (sh & 3) * 8;
+  uint4 r;
+  r.x = (uint32_t)((((uint64_t)w1 << 32) | w0) >> bs);
+  r.y = (uint32_t)((((uint64_t)w2 << 32) | w1) >> bs);
+  r.z = (uint32_t)((((uint64_t)w3 << 32) | w2) >> bs);
+  r.w = (uint32_t)((((uint64_t)w4 << 32) | w3) >> bs);
+  return r;
+}
+
+// One tile of a copy dst[0, n) <- src[0, n), laid over dst's 16-byte granules (stream_batch.h
+// tiles_of): this thread's granule is loaded, the block meets, the granule is stored.  A
+// granule that lies whole in [0, n) moves as one vector, the head and tail granules byte-wise.
+template <int THREADS>
+__device__ __forceinline__ void copy_tile(uint8_t *dst, const uint8_t *src, uint64_t n, uint64_t tile) {
+  const uint64_t mis = (uint64_t)((uintptr_t)dst & 15);
+  const uint64_t g = tile * THREADS + threadIdx.x;
+  const int64_t lo = (int64_t)(16 * g) - (int64_t)mis;   // the granule's first byte, as an offset in [0, n)
+  const bool whole = lo >= 0 && (uint64_t)lo + 16 <= n;
+  uint4 v = make_uint4(0, 0, 0, 0);
+  uint8_t b[16];
+  if (whole) {
+    v = load16_any(src + lo);
+  } else {
 #pragma unroll
-    for (int q = 0; q < 16; q++) v[q] = a + q < n ? buf[src + a + q] : 0;
-    __syncthreads();
+    for (int q = 0; q < 16; q++) b[q] = lo + q >= 0 && (uint64_t)(lo + q) < n ? src[lo + q] : 0;
+  }
+  __syncthreads();
+  if (whole) {
+    *reinterpret_cast<uint4 *>(dst + lo) = v;
+  } else {
 #pragma unroll
     for (int q = 0; q < 16; q++)
-      if (a + q < n) buf[a + q] = v[q];
-    __syncthreads();
+      if (lo + q >= 0 && (uint64_t)(lo + q) < n) dst[lo + q] = b[q];
   }
+  __syncthreads();
+}
+
+// Every due move of a round in one launch.  Block b does units[b]: the tiles tile0, tile0 +
+// step, ... of one descriptor in ascending order, each loaded whole before it is stored, so a
+// tile's stores (below its own sources, src > 0) cannot reach what a LATER tile of the same
+// block still has to read.  The host gives an overlapping move (src < n) one block, which then
+// owns every tile; without overlap no store lands in the source range and any split is safe
+// (stream_batch.h plan_moves).
+__global__ __launch_bounds__(kMoveThreads) void stream_move_batch_kernel(const MoveDesc *descs, const MoveUnit *units) {
+  const MoveUnit u = units[blockIdx.x];
+  const MoveDesc d = descs[u.desc];
+  const uint64_t tiles = tiles_of((uint64_t)(uintptr_t)d.buf, d.n, kMoveTile);
+  for (uint64_t t = u.tile0; t < tiles; t += u.step) copy_tile<kMoveThreads>(d.buf, d.buf + d.src, d.n, t);
+}
+
+// the one-move launch (a lone session's history and input moves): the same walk, the
+// descriptor in the arguments
+__global__ __launch_bounds__(kMoveThreads) void stream_move_kernel(uint8_t *buf, uint64_t src, uint64_t n, uint32_t step) {
+  const uint64_t tiles = tiles_of((uint64_t)(uintptr_t)buf, n, kMoveTile);
+  for (uint64_t t = blockIdx.x; t < tiles; t += step) copy_tile<kMoveThreads>(buf, buf + src, n, t);
+}
+
+// span[dst, dst + n) <- src[0, n) for every descriptor (blockIdx.y), its tiles over blockIdx.x.
+// Sources have any alignment; dst is a multiple of 16 and the span 16-byte aligned.
+__global__ __launch_bounds__(kGatherThreads) void stream_gather_kernel(const GatherDesc *descs, uint8_t *span) {
+  const GatherDesc d = descs[blockIdx.y];
+  const uint64_t tiles = tiles_of(0, d.n, kGatherTile);
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) copy_tile<kGatherThreads>(span + d.dst, d.src, d.n, t);
 }
 
 }  // namespace mib
 
 extern "C" hipError_t mib_decode_resume_launch(mib::StreamJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
-                                               int grid, int per_cu, hipStream_t stream) {
+                                               int grid, int per_cu, uint8_t *d_heads, hipStream_t stream) {
   if (per_cu <= 1)
-    hipLaunchKernelGGL(mib::decode_resume_kernel<true>, dim3(grid), dim3(64), 0, stream, d_jobs, njobs, d_scratch, per_block);
+    hipLaunchKernelGGL(mib::decode_resume_kernel<true>, dim3(grid), dim3(64), 0, stream, d_jobs, njobs, d_scratch, per_block, d_heads);
   else
-    hipLaunchKernelGGL(mib::decode_resume_kernel<false>, dim3(grid), dim3(64), 0, stream, d_jobs, njobs, d_scratch, per_block);
+    hipLaunchKernelGGL(mib::decode_resume_kernel<false>, dim3(grid), dim3(64), 0, stream, d_jobs, njobs, d_scratch, per_block, d_heads);
   return hipGetLastError();
 }
 
 extern "C" hipError_t mib_stream_move_launch(uint8_t *d_buf, uint64_t src, uint64_t n, hipStream_t stream) {
   if (n == 0 || src == 0) return hipSuccess;
-  const uint64_t tile = (uint64_t)mib::kMoveThreads * 16;
-  const uint64_t tiles = (n + tile - 1) / tile;
-  const int grid = src >= n ? (int)(tiles < 1024 ? tiles : 1024) : 1;
-  hipLaunchKernelGGL(mib::stream_move_kernel, dim3(grid), dim3(mib::kMoveThreads), 0, stream, d_buf, src, n);
+  const mib::MoveDesc d{d_buf, src, n};
+  std::vector<mib::MoveUnit> units;
+  mib::plan_moves(&d, 1, units);   // (one block when the ranges overlap)
+  const uint32_t grid = (uint32_t)units.size();
+  hipLaunchKernelGGL(mib::stream_move_kernel, dim3(grid), dim3(mib::kMoveThreads), 0, stream, d_buf, src, n, grid);
+  return hipGetLastError();
+}
+
+// n_units blocks (stream_batch.h plan_moves); both arrays on the device
+extern "C" hipError_t mib_stream_move_batch_launch(const mib::MoveDesc *d_descs, const mib::MoveUnit *d_units, uint32_t n_units,
+                                                   hipStream_t stream) {
+  if (n_units == 0) return hipSuccess;
+  hipLaunchKernelGGL(mib::stream_move_batch_kernel, dim3(n_units), dim3(mib::kMoveThreads), 0, stream, d_descs, d_units);
+  return hipGetLastError();
+}
+
+// k descriptors (<= kGatherMaxDescs), `blocks` blocks each (stream_batch.h gather_blocks)
+extern "C" hipError_t mib_stream_gather_launch(const mib::GatherDesc *d_descs, uint32_t k, uint32_t blocks, uint8_t *d_span,
+                                               hipStream_t stream) {
+  if (k == 0) return hipSuccess;
+  hipLaunchKernelGGL(mib::stream_gather_kernel, dim3(blocks, k), dim3(mib::kGatherThreads), 0, stream, d_descs, d_span);
   return hipGetLastError();
 }
 

@@ -19,10 +19,16 @@
 #include "common.h"
 #include "parts.h"
 #include "stream_session.h"
+#include "stream_batch.h"
 
+// (d_heads: null, or one checkpoint head per job, loaded before and stored after the job runs)
 extern "C" hipError_t mib_decode_resume_launch(mib::StreamJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
-                                               int grid, int per_cu, hipStream_t stream);
+                                               int grid, int per_cu, uint8_t *d_heads, hipStream_t stream);
 extern "C" hipError_t mib_stream_move_launch(uint8_t *d_buf, uint64_t src, uint64_t n, hipStream_t stream);
+extern "C" hipError_t mib_stream_move_batch_launch(const mib::MoveDesc *d_descs, const mib::MoveUnit *d_units, uint32_t n_units,
+                                                   hipStream_t stream);
+extern "C" hipError_t mib_stream_gather_launch(const mib::GatherDesc *d_descs, uint32_t k, uint32_t blocks, uint8_t *d_span,
+                                               hipStream_t stream);
 extern "C" hipError_t mib_decode_stream_init_tables(const int16_t *host_lut);
 extern "C" hipError_t mib_decode_parts_launch(mib::DecJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
                                               unsigned *d_ticket, int grid, int per_cu, hipStream_t stream);
@@ -325,6 +331,12 @@ struct mib_ctx {
   // part decoding: entries, positions, progress words, ticket (one allocation)
   uint8_t *d_parts = nullptr;
   uint64_t parts_bytes = 0;
+  // batches of decoder sessions (mib_decoder_update_batch): a round's jobs, checkpoint heads and
+  // move / gather descriptors, and the span the sessions' output is gathered into
+  uint8_t *d_sbatch = nullptr;
+  uint64_t sbatch_bytes = 0;
+  uint8_t *d_sspan = nullptr;
+  uint64_t sspan_bytes = 0;
   // encode workspaces (encode.hip): lane 0 on `stream`, lane l > 0 on lane_stream[l] (a batch
   // encode runs as concurrent parts, encode_streams)
   void *enc_ws = nullptr;
@@ -339,7 +351,7 @@ struct mib_ctx {
   struct Trim {
     uint64_t need = 0;
     int quiet = 0;   // trims in a row whose calls needed no more than the keep size
-  } stage_trim[kStageSlots], scratch_trim, parts_trim;
+  } stage_trim[kStageSlots], scratch_trim, parts_trim, sspan_trim;
   // pinned host ring of the host <-> device transfers (host_io below): two halves, one filling
   // on the host while the other is in flight; allocated once, 2 x kRingHalf
   uint8_t *ring = nullptr;
@@ -789,6 +801,8 @@ void mib_ctx_free(mib_ctx *c) {
   if (c->d_jobs) hipFree(c->d_jobs);
   if (c->d_aux) hipFree(c->d_aux);
   if (c->d_parts) hipFree(c->d_parts);
+  if (c->d_sbatch) hipFree(c->d_sbatch);
+  if (c->d_sspan) hipFree(c->d_sspan);
   for (int i = 0; i < kStageSlots; i++)
     if (c->stage[i]) hipFree(c->stage[i]);
   if (c->enc_ws) mib_encode_ws_free(c->enc_ws);
@@ -847,6 +861,7 @@ static void trim_default_ctx(mib_ctx *c) {
     if (!(streaming && i == 3)) release_large(&c->stage[i], &c->stage_cap[i], kKeepStage, c->stage_trim[i]);
   release_large(&c->d_scratch, &c->scratch_bytes, kKeepScratch, c->scratch_trim);
   release_large(&c->d_parts, &c->parts_bytes, kKeepScratch, c->parts_trim);
+  release_large(&c->d_sspan, &c->sspan_bytes, kKeepStage, c->sspan_trim);
   if (!streaming) {
     mib_encode_ws_trim(&c->enc_ws, kKeepScratch);
     for (int l = 0; l < kEncLanes; l++) mib_encode_ws_trim(&c->lane_ws[l], kKeepScratch);
@@ -859,6 +874,7 @@ void mib_ctx_trim(mib_ctx *c, uint64_t keep_stage, uint64_t keep_scratch) {
   for (int i = 0; i < kStageSlots; i++) release_large(&c->stage[i], &c->stage_cap[i], keep_stage, c->stage_trim[i]);
   release_large(&c->d_scratch, &c->scratch_bytes, keep_scratch, c->scratch_trim);
   release_large(&c->d_parts, &c->parts_bytes, keep_scratch, c->parts_trim);
+  release_large(&c->d_sspan, &c->sspan_bytes, keep_stage, c->sspan_trim);
   mib_encode_ws_trim(&c->enc_ws, keep_scratch);
   for (int l = 0; l < kEncLanes; l++) mib_encode_ws_trim(&c->lane_ws[l], keep_scratch);
 }
@@ -1297,12 +1313,14 @@ struct mib_decoder {
   uint64_t need_len = 0;              // pending bytes the next launch needs at least (0: unknown)
   int error = 0;
   bool finished = false;
+  bool ck_stale = false;              // the device checkpoint's head is behind `ck` (a batch call rebased the input)
   int device = 0;
 };
 
 namespace {
 int g_force_small_decoder = 0;   // mib_force_decoder_build
-constexpr size_t kCkHead = offsetof(mib::StreamCkpt, win);
+constexpr size_t kCkHead = mib::kStreamCkHead;
+static_assert(kCkHead == offsetof(mib::StreamCkpt, win), "the checkpoint head ends where the window starts");
 constexpr uint64_t kStreamScratch =
     (mib::kDecodeTableInts * 4 + mib::kDecodeCtxBytes + 1152 + 1152 * 4 + 1100 * 4 + 3092 * 4 + 255) & ~(uint64_t)255;
 
@@ -1337,7 +1355,8 @@ int decoder_open(mib_decoder *d, mib_ctx *c, uint8_t first) {
   return 0;
 }
 
-int decoder_append(mib_decoder *d, mib_ctx *c, const uint8_t *in, size_t n) {
+// room for n more bytes of pending input
+int decoder_reserve(mib_decoder *d, mib_ctx *c, size_t n) {
   if (d->in_len + n + 16 > d->in_cap) {
     const uint64_t cap = std::max<uint64_t>(2 * d->in_cap, std::max<uint64_t>(d->in_len + n + 16, 1 << 16));
     uint8_t *p = nullptr;
@@ -1353,6 +1372,12 @@ int decoder_append(mib_decoder *d, mib_ctx *c, const uint8_t *in, size_t n) {
     d->d_in = p;
     d->in_cap = cap;
   }
+  return 0;
+}
+
+int decoder_append(mib_decoder *d, mib_ctx *c, const uint8_t *in, size_t n) {
+  int rc0 = decoder_reserve(d, c, n);
+  if (rc0) return rc0;
   if (n) {
     const mib::HostPiece up{d->d_in + d->in_len, in, n};
     int rc = mib::ctx_upload(c, c->stream, &up, 1);
@@ -1364,6 +1389,7 @@ int decoder_append(mib_decoder *d, mib_ctx *c, const uint8_t *in, size_t n) {
 
 int decoder_put_ckpt(mib_decoder *d, mib_ctx *c) {
   HIP_OK(hipMemcpyAsync(d->d_ck, &d->ck, kCkHead, hipMemcpyHostToDevice, c->stream));
+  d->ck_stale = false;
   return 0;
 }
 
@@ -1377,6 +1403,9 @@ int decoder_run(mib_decoder *d, mib_ctx *c, int final, std::vector<uint8_t> &got
     if (delta) {
       HIP_OK(mib_stream_move_launch(d->d_buf, delta, d->ck.e.pos - delta, c->stream));
       mib::stream_rebase_output(&d->ck, delta);
+      int rc = decoder_put_ckpt(d, c);
+      if (rc) return rc;
+    } else if (d->ck_stale) {
       int rc = decoder_put_ckpt(d, c);
       if (rc) return rc;
     }
@@ -1395,7 +1424,8 @@ int decoder_run(mib_decoder *d, mib_ctx *c, int final, std::vector<uint8_t> &got
     j.final = final;
     HIP_OK(hipMemcpyAsync(d->d_job, &j, sizeof(j), hipMemcpyHostToDevice, c->stream));
     HIP_OK(mib_decode_resume_launch(d->d_job, 1, d->d_scratch, kStreamScratch, 1,
-                                    __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, 1), c->stream));
+                                    __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, 1), nullptr,
+                                    c->stream));
     HIP_OK(hipMemcpyAsync(&j, d->d_job, sizeof(j), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipMemcpyAsync(&d->ck, d->d_ck, kCkHead, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -1453,9 +1483,305 @@ int decoder_result(mib_decoder *d, int rc, std::vector<uint8_t> &got, mib_buf *o
   }
   return rc;
 }
+
+// ---------------------------------------------------------------- batches of sessions
+// mib_decoder_update_batch / finish_batch: the sessions of a call advance in rounds, and a round
+// is decoder_run's loop body for every session that still has a launch to make -- with one
+// upload (jobs, checkpoint heads, move descriptors), one move launch, ONE decode launch, one
+// read-back (jobs and heads), one gather launch and one download, however many sessions.
+// A session's job has exactly the parameters its solo launch would have, so its returns, its
+// passes and its redecoded bytes are the solo call's (stream_batch.h holds the planning).
+uint64_t g_batch_launches = 0;   // mib_decoder_batch_stats
+int g_decoder_grid_cap = 0;      // mib_force_decoder_grid
+double g_batch_ms[5];            // mib_decoder_batch_times: upload, launch, read-back, gather, download
+
+struct BatchSlot {
+  mib_decoder *d = nullptr;
+  int rc = 0;
+  bool run = false;       // has a launch to make in the next round
+  bool suspended = false; // left on kStreamNeedInput: its pending input may be compacted
+  uint64_t start = 0, n = 0;
+  int status = 0;
+  std::vector<uint8_t> got;
+};
+
+double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+  return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+// the moves' descriptors at host[at] and their blocks (plan_moves) behind them; returns where the blocks start
+uint64_t stage_moves(const std::vector<mib::MoveDesc> &moves, std::vector<mib::MoveUnit> &units, uint64_t at,
+                     std::vector<uint8_t> &host) {
+  mib::plan_moves(moves.data(), moves.size(), units);
+  const uint64_t units_at = (at + moves.size() * sizeof(mib::MoveDesc) + 15) & ~15ull;
+  host.resize(units_at + units.size() * sizeof(mib::MoveUnit));
+  if (!moves.empty()) memcpy(host.data() + at, moves.data(), moves.size() * sizeof(mib::MoveDesc));
+  if (!units.empty()) memcpy(host.data() + units_at, units.data(), units.size() * sizeof(mib::MoveUnit));
+  return units_at;
+}
+
+// the rounds of one call over the slots with `run` set; a non-zero return is a device failure
+// that ends every session still in a round
+int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final) {
+  using clk = std::chrono::steady_clock;
+  std::vector<size_t> act;
+  for (size_t i = 0; i < slots.size(); i++) {
+    BatchSlot &s = slots[i];
+    if (!s.run) continue;
+    // the last launch stopped in front of a raw or metadata block that is still not whole
+    if (!mib::stream_enters_round(final != 0, s.d->in_len, s.d->need_len)) s.run = false;
+    else act.push_back(i);
+  }
+  const int cus = (c->device >= 0 && c->device < kMaxDevices && g_dev_cus[c->device] > 0) ? g_dev_cus[c->device] : 256;
+  std::vector<uint8_t> host, span;
+  std::vector<mib::MoveDesc> moves;
+  std::vector<mib::MoveUnit> units;
+  std::vector<mib::GatherDesc> gd;
+  std::vector<uint64_t> len, dst;
+  int rc;
+  while (!act.empty()) {
+    const auto t0 = clk::now();
+    const size_t k = act.size();
+    // [jobs][heads][move descriptors][move units]: one upload; the first two come back
+    const uint64_t heads_at = mib::stream_heads_offset(k, sizeof(mib::StreamJob));
+    const uint64_t moves_at = (heads_at + k * kCkHead + 15) & ~15ull;
+    host.assign(moves_at, 0);
+    moves.clear();
+    for (size_t a = 0; a < k; a++) {
+      BatchSlot &s = slots[act[a]];
+      mib_decoder *d = s.d;
+      // the history to the buffer's front: the next launch needs out_window + slack behind pos
+      const uint64_t delta = mib::stream_compact_delta(d->ck.e.pos, d->lgwin);
+      if (delta) {
+        moves.push_back(mib::MoveDesc{d->d_buf, delta, d->ck.e.pos - delta});
+        mib::stream_rebase_output(&d->ck, delta);
+      }
+      s.start = d->ck.e.pos;
+      mib::StreamJob j;
+      memset(&j, 0, sizeof(j));
+      j.in = d->d_in;
+      j.in_len = d->in_len;
+      j.buf = d->d_buf;
+      j.buf_cap = d->buf_cap;
+      j.out_limit = s.start + d->out_window;
+      j.dict = d->d_dict;
+      j.dict_len = d->has_dict ? d->dict.size() : 0;
+      j.ck = d->d_ck;
+      j.lgwin = d->lgwin;
+      j.final = final;
+      memcpy(host.data() + a * sizeof(j), &j, sizeof(j));
+      memcpy(host.data() + heads_at + a * kCkHead, &d->ck, kCkHead);
+    }
+    const uint64_t units_at = stage_moves(moves, units, moves_at, host);
+    if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, host.size())) != 0) return rc;
+    const int per_cu = __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, k);
+    const int grid = mib::stream_batch_grid(k, cus, per_cu, __atomic_load_n(&g_decoder_grid_cap, __ATOMIC_RELAXED));
+    c->scratch_trim.need = std::max(c->scratch_trim.need, kStreamScratch * (uint64_t)grid);
+    if ((rc = grow((void **)&c->d_scratch, &c->scratch_bytes, kStreamScratch * (uint64_t)grid)) != 0) return rc;
+    HIP_OK(hipMemcpyAsync(c->d_sbatch, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(mib_stream_move_batch_launch((const mib::MoveDesc *)(c->d_sbatch + moves_at), (const mib::MoveUnit *)(c->d_sbatch + units_at),
+                                        (uint32_t)units.size(), c->stream));
+    const auto t1 = clk::now();
+    HIP_OK(mib_decode_resume_launch((mib::StreamJob *)c->d_sbatch, (int)k, c->d_scratch, kStreamScratch, grid, per_cu,
+                                    c->d_sbatch + heads_at, c->stream));
+    __atomic_add_fetch(&g_batch_launches, 1, __ATOMIC_RELAXED);
+    // (waiting here, not in the copy, costs nothing -- the copy into pageable memory waits for the
+    // launch anyway -- and lets mib_decoder_batch_times tell the launch from the read-back)
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const auto t2 = clk::now();
+    HIP_OK(hipMemcpyAsync(host.data(), c->d_sbatch, heads_at + k * kCkHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const auto t3 = clk::now();
+    // each session's launch, as decoder_run reads it
+    for (size_t a = 0; a < k; a++) {
+      BatchSlot &s = slots[act[a]];
+      mib_decoder *d = s.d;
+      mib::StreamJob j;
+      memcpy(&j, host.data() + a * sizeof(j), sizeof(j));
+      memcpy(&d->ck, host.data() + heads_at + a * kCkHead, kCkHead);
+      d->ck_stale = false;
+      d->passes++;
+      s.status = j.status;
+      s.n = 0;
+      if (j.status == mib::kStreamNeedInput && j.redone > 0) d->redone += (uint64_t)j.redone;
+      if (j.status < 0) { s.rc = j.status; continue; }
+      if (j.out_pos < (int64_t)s.start || (uint64_t)j.out_pos > d->buf_cap) { s.rc = MIB_E_NO_PROGRESS; continue; }
+      s.n = (uint64_t)j.out_pos - s.start;
+      d->total_out += s.n;
+      if (d->max_out >= 0 && d->total_out > (uint64_t)d->max_out) { s.rc = MIB_E_OUTPUT_LIMIT; s.n = 0; continue; }
+      if (j.status == mib::kStreamNeedInput && !final) d->need_len = j.need_len > 0 ? (uint64_t)j.need_len : 0;
+    }
+    // every session's [start, out_pos) to the staging span, the span down in one copy
+    gd.clear();
+    len.clear();
+    std::vector<size_t> who;
+    for (size_t a = 0; a < k; a++)
+      if (slots[act[a]].n) {
+        who.push_back(act[a]);
+        len.push_back(slots[act[a]].n);
+      }
+    auto t4 = t3, t5 = t3;
+    if (!who.empty()) {
+      dst.resize(who.size());
+      const uint64_t total = mib::plan_gather(len.data(), len.size(), dst.data());
+      for (size_t g = 0; g < who.size(); g++)
+        gd.push_back(mib::GatherDesc{slots[who[g]].d->d_buf + slots[who[g]].start, len[g], dst[g]});
+      c->sspan_trim.need = std::max(c->sspan_trim.need, total);
+      if ((rc = grow((void **)&c->d_sspan, &c->sspan_bytes, total)) != 0) return rc;
+      // (the descriptors take the place of the jobs, which are read: never more of them, never larger)
+      static_assert(sizeof(mib::GatherDesc) <= sizeof(mib::StreamJob), "gather descriptors fit where the jobs were");
+      HIP_OK(hipMemcpyAsync(c->d_sbatch, gd.data(), gd.size() * sizeof(mib::GatherDesc), hipMemcpyHostToDevice, c->stream));
+      for (size_t g0 = 0; g0 < gd.size(); g0 += mib::kGatherMaxDescs) {
+        const size_t g1 = std::min(gd.size(), g0 + mib::kGatherMaxDescs);
+        HIP_OK(mib_stream_gather_launch((const mib::GatherDesc *)c->d_sbatch + g0, (uint32_t)(g1 - g0),
+                                        mib::gather_blocks(len.data() + g0, g1 - g0), c->d_sspan, c->stream));
+      }
+      t4 = clk::now();
+      span.resize(total);
+      const mib::HostPiece down{span.data(), c->d_sspan, total};
+      if ((rc = mib::ctx_download(c, c->stream, &down, 1)) != 0) return rc;
+      for (size_t g = 0; g < who.size(); g++) {
+        std::vector<uint8_t> &got = slots[who[g]].got;
+        got.insert(got.end(), span.begin() + dst[g], span.begin() + dst[g] + len[g]);
+      }
+      t5 = clk::now();
+    }
+    g_batch_ms[0] += ms_between(t0, t1);
+    g_batch_ms[1] += ms_between(t1, t2);
+    g_batch_ms[2] += ms_between(t2, t3);
+    g_batch_ms[3] += ms_between(t3, t4);
+    g_batch_ms[4] += ms_between(t4, t5);
+    // who goes on
+    std::vector<size_t> next;
+    for (size_t a = 0; a < k; a++) {
+      BatchSlot &s = slots[act[a]];
+      mib_decoder *d = s.d;
+      s.run = false;
+      if (s.rc) continue;
+      if (s.status == mib::kStreamFinished) {
+        d->finished = true;
+        // bytes behind the stream's end: refused, as one-shot decoding refuses them (-17)
+        if (d->in_len > ((d->ck.e.bit + 7) >> 3)) s.rc = -17;
+      } else if (s.status == mib::kStreamNeedOutput) {   // (the checkpoint is where the launch left)
+        s.run = true;
+        next.push_back(act[a]);
+      } else if (s.status != mib::kStreamNeedInput || final) {
+        s.rc = MIB_E_NO_PROGRESS;
+      } else {
+        s.suspended = true;
+      }
+    }
+    act.swap(next);
+  }
+  // input no resume reads again leaves the front of the pending bytes (once it is worth a move):
+  // every session's move in one launch
+  moves.clear();
+  for (BatchSlot &s : slots) {
+    if (!s.suspended || s.rc) continue;
+    mib_decoder *d = s.d;
+    const uint64_t keep = mib::stream_keep_from(d->ck);
+    if (keep >= (64u << 10) && 2 * keep >= d->in_len) {
+      moves.push_back(mib::MoveDesc{d->d_in, keep, d->in_len - keep});
+      d->in_len -= keep;
+      d->need_len = d->need_len > keep ? d->need_len - keep : 0;
+      mib::stream_rebase_input(&d->ck, keep);
+      d->ck_stale = true;   // the next launch brings the head: a batch's with its jobs, a solo one's first
+    }
+  }
+  if (!moves.empty()) {
+    host.clear();
+    const uint64_t units_at = stage_moves(moves, units, 0, host);
+    if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, host.size())) != 0) return rc;
+    HIP_OK(hipMemcpyAsync(c->d_sbatch, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(mib_stream_move_batch_launch((const mib::MoveDesc *)c->d_sbatch, (const mib::MoveUnit *)(c->d_sbatch + units_at),
+                                        (uint32_t)units.size(), c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+
+// update (in != null) or finish (in == null) of k sessions
+int decoder_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *out, int *status, bool finish) {
+  if (k == 0) return 0;
+  if (!d || !out || !status || (!finish && !in)) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++)
+    if (!d[i] || (!finish && !in[i].data && in[i].size)) return MIB_E_INVALID_ARG;
+  {
+    std::vector<const mib_decoder *> seen(d, d + k);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return MIB_E_INVALID_ARG;
+  }
+  // what each session's solo call would do before it needs the device
+  bool device = false;
+  for (size_t i = 0; i < k; i++)
+    if (!d[i]->error && !d[i]->finished && (finish || in[i].size)) device = true;
+  struct Hold {   // (the default context for the whole call, taken only when a session needs the device)
+    bool on = false;
+    ~Hold() { if (on) mib_default_lock(0); }
+  } hold;
+  mib_ctx *c = nullptr;
+  if (device) {
+    mib_default_lock(1);
+    hold.on = true;
+    c = default_ctx();
+    if (!c) return MIB_E_NO_DEVICE;
+    hipSetDevice(c->device);
+  }
+  std::vector<BatchSlot> slots(k);
+  std::vector<mib::HostPiece> up;
+  for (size_t i = 0; i < k; i++) {
+    BatchSlot &s = slots[i];
+    s.d = d[i];
+    out[i].data = nullptr;
+    out[i].size = 0;
+    status[i] = 0;
+    if (d[i]->error) continue;
+    if (finish ? d[i]->finished : in[i].size == 0) continue;   // returns 0 and nothing
+    if (d[i]->finished) { s.rc = -17; continue; }
+    d[i]->device = c->device;
+    // no byte at all (finish): the decoder reads an empty input's padding, window bits 0 (16) first
+    if (!d[i]->lgwin) s.rc = decoder_open(d[i], c, finish ? 0 : in[i].data[0]);
+    if (!s.rc) s.rc = decoder_reserve(d[i], c, finish ? 0 : in[i].size);
+    if (s.rc) continue;
+    if (!finish) {
+      up.push_back(mib::HostPiece{d[i]->d_in + d[i]->in_len, in[i].data, in[i].size});
+      d[i]->in_len += in[i].size;
+    }
+    s.run = true;
+  }
+  int rc = 0;
+  if (!up.empty()) rc = mib::ctx_upload(c, c->stream, up.data(), up.size());
+  if (!rc && c) rc = decoder_batch_rounds(c, slots, finish ? 1 : 0);
+  for (size_t i = 0; i < k; i++) {
+    BatchSlot &s = slots[i];
+    if (d[i]->error) { status[i] = d[i]->error; continue; }
+    if (rc && s.run) s.rc = rc;   // a device failure ends the sessions that still had a launch to make
+    status[i] = decoder_result(d[i], s.rc, s.got, &out[i]);
+  }
+  return 0;
+}
 }  // namespace
 
 extern "C" {
+
+int mib_decoder_update_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *out, int *status) {
+  if (k && !in) return MIB_E_INVALID_ARG;
+  return decoder_batch(d, in, k, out, status, false);
+}
+
+int mib_decoder_finish_batch(mib_decoder *const *d, size_t k, mib_buf *out, int *status) {
+  return decoder_batch(d, nullptr, k, out, status, true);
+}
+
+void mib_decoder_batch_stats(uint64_t *launches) {
+  if (launches) *launches = __atomic_load_n(&g_batch_launches, __ATOMIC_RELAXED);
+}
+
+void mib_decoder_batch_times(double *ms, int n) {
+  for (int i = 0; ms && i < n; i++) ms[i] = i < 5 ? g_batch_ms[i] : 0;
+}
+
+void mib_force_decoder_grid(int max_blocks) { __atomic_store_n(&g_decoder_grid_cap, max_blocks > 0 ? max_blocks : 0, __ATOMIC_RELAXED); }
 
 void mib_dec_opts_default(mib_dec_opts *o) {
   if (!o) return;

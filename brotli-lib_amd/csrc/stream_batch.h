@@ -1,0 +1,101 @@
+// Batches of streaming decoder sessions (mib_decoder_update_batch, DESIGN.md §4d "Batches of
+// sessions"): the descriptors the host and the batch kernels of decode_stream.hip share, and the
+// planning of a round -- which sessions launch, where each session's output lies in the staging
+// span, which block moves which tiles, how large the decode grid is.  Plain C++ (no HIP types):
+// the planning is exercised by a stand-alone host program under sanitizers
+// (tests/stream_batch_host_main.cpp).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+namespace mib {
+
+// buf[0, n) <- buf[src, src + n), src > 0 (a session's history, or its pending input, moves to
+// the front of its buffer); the ranges overlap when src < n
+struct MoveDesc {
+  uint8_t *buf;
+  uint64_t src, n;
+};
+// One block of the move launch: tiles tile0, tile0 + step, ... of descriptor `desc`, ascending.
+struct MoveUnit {
+  uint32_t desc, tile0, step, reserved;
+};
+// span[dst, dst + n) <- src[0, n): a session's new output goes to the staging span
+struct GatherDesc {
+  const uint8_t *src;
+  uint64_t n, dst;
+};
+
+constexpr int kMoveThreads = 1024;
+constexpr uint64_t kMoveTile = (uint64_t)kMoveThreads * 16;
+constexpr uint32_t kMoveSpread = 64;   // blocks a non-overlapping move is spread over at most
+constexpr int kGatherThreads = 256;
+constexpr uint64_t kGatherTile = (uint64_t)kGatherThreads * 16;
+constexpr uint32_t kGatherSpread = 256;   // blocks per descriptor at most (each walks its tiles)
+constexpr size_t kGatherMaxDescs = 65535;   // descriptors per launch (the grid's y extent)
+
+// Tiles are laid over the destination's 16-byte granules: tile t holds the granules
+// [t * kMoveThreads, (t + 1) * kMoveThreads), granule g the destination bytes
+// [16 g - mis, 16 g - mis + 16) that lie in [0, n), where mis = the buffer address mod 16.
+constexpr uint64_t tiles_of(uint64_t mis, uint64_t n, uint64_t tile) { return n ? (n + (mis & 15) + tile - 1) / tile : 0; }
+
+// The move launch's blocks.  An overlapping move has ONE block, which owns every tile in
+// ascending order (a tile is loaded whole before it is stored, so its stores, below its own
+// sources, cannot reach what a later tile still reads); without overlap no store lands in the
+// source range and the tiles are spread over up to kMoveSpread blocks.  Empty moves and
+// src = 0 (nothing to do) get no block.
+inline void plan_moves(const MoveDesc *d, size_t k, std::vector<MoveUnit> &units) {
+  units.clear();
+  for (size_t i = 0; i < k; i++) {
+    if (d[i].n == 0 || d[i].src == 0) continue;
+    const uint64_t tiles = tiles_of((uint64_t)(uintptr_t)d[i].buf, d[i].n, kMoveTile);
+    const uint32_t nb = d[i].src < d[i].n ? 1u : (uint32_t)(tiles < kMoveSpread ? tiles : kMoveSpread);
+    for (uint32_t b = 0; b < nb; b++) units.push_back(MoveUnit{(uint32_t)i, b, nb, 0});
+  }
+}
+
+// Where each session's [start, out_pos) goes in the staging span: dense, in session order,
+// each range starting on a 16-byte boundary (the gather kernel stores whole 16-byte vectors).
+// Returns the span's size.
+inline uint64_t plan_gather(const uint64_t *len, size_t k, uint64_t *dst) {
+  uint64_t at = 0;
+  for (size_t i = 0; i < k; i++) {
+    dst[i] = at;
+    at += (len[i] + 15) & ~15ull;
+  }
+  return at;
+}
+// blocks per descriptor (the grid's x extent) of a gather launch over these lengths
+inline uint32_t gather_blocks(const uint64_t *len, size_t k) {
+  uint64_t most = 1;
+  for (size_t i = 0; i < k; i++) {
+    const uint64_t t = tiles_of(0, len[i], kGatherTile);
+    if (t > most) most = t;
+  }
+  return (uint32_t)(most < kGatherSpread ? most : kGatherSpread);
+}
+
+// A session launches in the first round of a call unless its last launch stopped in front of a
+// raw or metadata block that is still not whole (decoder_run's first line); later rounds take
+// the sessions whose launch stopped on the output limit.
+inline bool stream_enters_round(bool final, uint64_t in_len, uint64_t need_len) { return final || in_len >= need_len; }
+
+// The decode launch's grid: a block per job up to cus x per_cu resident waves, and `cap`
+// (mib_force_decoder_grid, 0: none) below that; the kernel's job loop takes the rest.
+inline int stream_batch_grid(size_t jobs, int cus, int per_cu, int cap) {
+  if (jobs == 0) return 0;
+  if (cus < 1) cus = 1;
+  if (per_cu < 1) per_cu = 1;
+  uint64_t g = (uint64_t)cus * (uint64_t)per_cu;
+  if (jobs < g) g = jobs;
+  if (cap > 0 && (uint64_t)cap < g) g = (uint64_t)cap;
+  return (int)g;
+}
+
+// The round's read-back array: k jobs, then k checkpoint heads (the bytes of a StreamCkpt in
+// front of its window), one device-to-host copy for both.
+inline uint64_t stream_heads_offset(size_t k, size_t job_bytes) { return ((uint64_t)k * job_bytes + 15) & ~15ull; }
+
+}  // namespace mib

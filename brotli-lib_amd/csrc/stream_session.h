@@ -35,6 +35,9 @@ struct StreamCkpt {
                            // has are laid over it when a launch resumes
 };
 static_assert(sizeof(StreamCkpt) == 72 + 24 + kStreamWin, "stream checkpoint layout");
+// the checkpoint without its window: what the host mirrors and a batch launch carries beside its jobs
+constexpr size_t kStreamCkHead = sizeof(StreamCkpt) - kStreamWin;
+static_assert(kStreamCkHead % 8 == 0, "checkpoint heads are copied in 8-byte words");
 
 // what a launch reports (negative: the decoder's error code)
 constexpr int kStreamNeedInput = 1;    // suspended: a command or header reaches past the input

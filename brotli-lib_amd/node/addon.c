@@ -298,6 +298,98 @@ static napi_value js_decoder_finished(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* a session's error as the BrotliDecoder methods throw it, as a value (the slot of a batch) */
+static napi_value decoder_error(napi_env env, int rc, const mib_buf *b) {
+  napi_value err = NULL, msg;
+  if (rc == MIB_E_OUTPUT_LIMIT) {   /* index.js rewrites the message, as for update() */
+    napi_value sz;
+    napi_create_string_utf8(env, "Decompressed size exceeds limit", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_create_int64(env, (int64_t)b->size, &sz);
+    napi_set_named_property(env, err, "size", sz);
+  } else if (rc == MIB_E_JS_TYPE_ERROR) {
+    napi_create_string_utf8(env, "Cannot read property 'subarray' of undefined", NAPI_AUTO_LENGTH, &msg);
+    napi_create_type_error(env, NULL, msg, &err);
+  } else if (rc == MIB_E_JS_RANGE_ERROR) {
+    napi_create_string_utf8(env, "offset is out of bounds", NAPI_AUTO_LENGTH, &msg);
+    napi_create_range_error(env, NULL, msg, &err);
+  } else {
+    napi_create_string_utf8(env, mib_strerror(rc), NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+  }
+  return err;
+}
+
+/* decoderUpdateBatch([handle...], [bytes...]) / decoderFinishBatch([handle...]) -> one Buffer or
+ * Error per session: the sessions advance in shared launches (mib_decoder_update_batch) */
+static napi_value decoder_batch(napi_env env, napi_callback_info info, int finish) {
+  size_t argc = 2;
+  napi_value argv[2], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  uint32_t k = 0, kc = 0;
+  bool is_arr = false, is_arr2 = finish != 0;
+  if (argc < (finish ? 1u : 2u) || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr ||
+      (!finish && (napi_is_array(env, argv[1], &is_arr2) != napi_ok || !is_arr2))) {
+    napi_throw_type_error(env, NULL, finish ? "decoderFinishBatch(decoders: BrotliDecoder[])"
+                                            : "decoderUpdateBatch(decoders: BrotliDecoder[], chunks: Uint8Array[])");
+    return NULL;
+  }
+  CHECK(env, napi_get_array_length(env, argv[0], &k));
+  if (!finish) {
+    CHECK(env, napi_get_array_length(env, argv[1], &kc));
+    if (kc != k) {
+      napi_throw_type_error(env, NULL, "decoderUpdateBatch: one chunk per decoder");
+      return NULL;
+    }
+  }
+  mib_decoder **hs = (mib_decoder **)calloc(k ? k : 1, sizeof(mib_decoder *));
+  mib_span *in = (mib_span *)calloc(k ? k : 1, sizeof(mib_span));
+  mib_buf *res = (mib_buf *)calloc(k ? k : 1, sizeof(mib_buf));
+  int *st = (int *)calloc(k ? k : 1, sizeof(int));
+  for (uint32_t i = 0; i < k; i++) {
+    napi_value e;
+    void *h = NULL;
+    napi_get_element(env, argv[0], i, &e);
+    int bad = napi_get_value_external(env, e, &h) != napi_ok || !h;
+    if (!bad && !finish) {
+      napi_get_element(env, argv[1], i, &e);
+      bad = get_bytes(env, e, &in[i].data, &in[i].size);
+    }
+    if (bad) {
+      free(hs), free(in), free(res), free(st);
+      napi_throw_type_error(env, NULL, "decoder batch: BrotliDecoder handles and Uint8Array chunks");
+      return NULL;
+    }
+    hs[i] = (mib_decoder *)h;
+  }
+  int rc = finish ? mib_decoder_finish_batch(hs, k, res, st) : mib_decoder_update_batch(hs, in, k, res, st);
+  free(hs), free(in);
+  if (rc) {
+    free(res), free(st);
+    return throw_code(env, rc);
+  }
+  napi_create_array_with_length(env, k, &out);
+  for (uint32_t i = 0; i < k; i++) {
+    napi_value v;
+    if (st[i]) {
+      v = decoder_error(env, st[i], &res[i]);
+      mib_buf_free(&res[i]);
+    } else {
+      v = take(env, &res[i]);
+    }
+    if (!v) {
+      for (uint32_t j = i + 1; j < k; j++) mib_buf_free(&res[j]);
+      out = NULL;
+      break;
+    }
+    napi_set_element(env, out, i, v);
+  }
+  free(res), free(st);
+  return out;
+}
+static napi_value js_decoder_update_batch(napi_env env, napi_callback_info info) { return decoder_batch(env, info, 0); }
+static napi_value js_decoder_finish_batch(napi_env env, napi_callback_info info) { return decoder_batch(env, info, 1); }
+
 /* encodeBatch([bytes...], quality, lgwin, mode, gpus, dictionary|null) -> [Buffer...]: one GPU
  * launch sequence (gpus >= 0: sharded over that many GPUs, 0 = all; -1 / absent: the default
  * device) */
@@ -578,6 +670,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"decoderUpdate", 0, js_decoder_update, 0, 0, 0, napi_default, 0},
       {"decoderFinish", 0, js_decoder_finish, 0, 0, 0, napi_default, 0},
       {"decoderFinished", 0, js_decoder_finished, 0, 0, 0, napi_default, 0},
+      {"decoderUpdateBatch", 0, js_decoder_update_batch, 0, 0, 0, napi_default, 0},
+      {"decoderFinishBatch", 0, js_decoder_finish_batch, 0, 0, 0, napi_default, 0},
       {"encodeBatch", 0, js_encode_batch, 0, 0, 0, napi_default, 0},
       {"encodeBatchAsync", 0, js_encode_batch_async, 0, 0, 0, napi_default, 0},
       {"decodeBatchAsync", 0, js_decode_batch_async, 0, 0, 0, napi_default, 0},

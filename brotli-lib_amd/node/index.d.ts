@@ -75,6 +75,10 @@ export declare function brotliEncodeBatch(inputs: Uint8Array[], options?: Brotli
 export declare function brotliEncodeBatchAsync(inputs: Uint8Array[], options?: BrotliEncodeOptions & BatchOptions): Promise<Uint8Array[]>
 /** a stream that fails to decode resolves to its Error in its slot */
 export declare function brotliDecodeBatchAsync(inputs: Uint8Array[], options?: BatchOptions): Promise<(Uint8Array | Error)[]>
+/** many distinct BrotliDecoder sessions advance by one chunk each in shared GPU launches; per slot what decoder.update(chunk) alone would have returned, or the Error it would have thrown */
+export declare function brotliDecoderUpdateBatch(decoders: BrotliDecoder[], chunks: Uint8Array[]): (Uint8Array | Error)[]
+/** finish() of many BrotliDecoder sessions in shared launches; per slot the rest of the output, or the Error of an incomplete stream */
+export declare function brotliDecoderFinishBatch(decoders: BrotliDecoder[]): (Uint8Array | Error)[]
 /** WOFF2 'glyf' transform (W3C WOFF2 section 5.1) of a TrueType font, on the GPU: FONT-mode input for brotliEncode */
 export declare function woff2TransformGlyf(ttf: Uint8Array): Uint8Array
 /** WOFF2 'hmtx' transform (section 5.4), or null when the table must stay untransformed */

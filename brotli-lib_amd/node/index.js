@@ -113,6 +113,23 @@ class BrotliDecoder {
   }
 }
 
+// Many BrotliDecoder sessions advanced by one chunk each in shared launches (a round is one
+// decode launch over every session that still has work).  One result per slot: the bytes
+// decoder.update(chunk) / decoder.finish() alone would have returned, or the Error it would have
+// thrown (not thrown here: the other sessions go on).  The decoders must be distinct.
+function decoderSlots(decoders, outs) {
+  return outs.map((o, i) => {
+    if (!(o instanceof Error)) return toU8(o)
+    return o.size !== undefined ? new Error(`Decompressed size ${o.size} exceeds limit ${decoders[i]._max}`) : o
+  })
+}
+function brotliDecoderUpdateBatch(decoders, chunks) {
+  return decoderSlots(decoders, native.decoderUpdateBatch(decoders.map((d) => d._h), chunks))
+}
+function brotliDecoderFinishBatch(decoders) {
+  return decoderSlots(decoders, native.decoderFinishBatch(decoders.map((d) => d._h)))
+}
+
 // options.gpus: shard the batch over that many GPUs (0: every visible one); absent: one GPU
 function gpusOf(options) {
   const g = options && options.gpus
@@ -157,5 +174,6 @@ function woff2ReconstructHmtx(data, glyf, loca, numGlyphs, numHMetrics) {
 module.exports = {
   brotliEncode, BrotliEncoder, brotliDecode, BrotliDecoder, brotliDecodedSize, EncoderMode,
   brotliEncodeBatch, brotliEncodeBatchAsync, brotliDecodeBatchAsync,
+  brotliDecoderUpdateBatch, brotliDecoderFinishBatch,
   woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx,
 }

@@ -17,7 +17,8 @@ import ctypes
 import os
 
 __all__ = ['brotliEncode', 'BrotliEncoder', 'brotliDecode', 'BrotliDecoder', 'brotliDecodedSize', 'EncoderMode', 'BrotliError',
-           'encode_batch', 'decode_batch', 'encoder_update_batch', 'DeviceContext', 'library_path']
+           'encode_batch', 'decode_batch', 'encoder_update_batch', 'decoder_update_batch', 'decoder_finish_batch',
+           'DeviceContext', 'library_path']
 
 _PKG = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # BROTLI_AMD_LIB: an instrumented build of the same library (timing experiments only)
@@ -143,6 +144,17 @@ def _L():
             lib.mib_force_decoder_build.argtypes = [ctypes.c_int]
             lib.mib_force_decoder_build.restype = None
             lib.mib_decoder_free.argtypes = [ctypes.c_void_p]
+        if hasattr(lib, 'mib_decoder_update_batch'):
+            lib.mib_decoder_update_batch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_Span), ctypes.c_size_t,
+                                                     ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
+            lib.mib_decoder_finish_batch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.POINTER(_Buf),
+                                                     ctypes.POINTER(ctypes.c_int)]
+            lib.mib_decoder_batch_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+            lib.mib_decoder_batch_stats.restype = None
+            lib.mib_decoder_batch_times.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+            lib.mib_decoder_batch_times.restype = None
+            lib.mib_force_decoder_grid.argtypes = [ctypes.c_int]
+            lib.mib_force_decoder_grid.restype = None
         lib.mib_encode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
                                          ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_decode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Buf),
@@ -394,6 +406,44 @@ class BrotliDecoder:
         if getattr(self, '_h', None):
             _L().mib_decoder_free(self._h)
             self._h = None
+
+
+def _decoder_batch_results(decoders, rc, outs, st):
+    if rc:
+        raise _err(rc)
+    res = []
+    for i, d in enumerate(decoders):
+        try:
+            res.append(d._result(st[i], outs[i]))
+        except BrotliError as e:
+            res.append(e)
+    return res
+
+
+def decoder_update_batch(decoders, chunks):
+    """Advance many BrotliDecoder sessions by one chunk each: a round is one decode launch over
+    every session that still has work (mib_decoder_update_batch).  Returns a list with, per
+    slot, the bytes decoder.update(chunk) alone would have returned, or the BrotliError it would
+    have raised (not raised here: the other sessions go on).  The decoders must be distinct."""
+    k = len(decoders)
+    if len(chunks) != k:
+        raise ValueError('decoder_update_batch: %d decoders, %d chunks' % (k, len(chunks)))
+    keep = [_in(b) for b in chunks]
+    hs = (ctypes.c_void_p * k)(*[d._h for d in decoders])
+    spans = (_Span * k)(*[_Span(_addr(a) if n else None, n) for a, n, _ in keep])
+    outs = (_Buf * k)()
+    st = (ctypes.c_int * k)()
+    return _decoder_batch_results(decoders, _L().mib_decoder_update_batch(hs, spans, k, outs, st), outs, st)
+
+
+def decoder_finish_batch(decoders):
+    """finish() of many BrotliDecoder sessions in shared launches (mib_decoder_finish_batch):
+    per slot the rest of the output, or the BrotliError of an incomplete stream."""
+    k = len(decoders)
+    hs = (ctypes.c_void_p * k)(*[d._h for d in decoders])
+    outs = (_Buf * k)()
+    st = (ctypes.c_int * k)()
+    return _decoder_batch_results(decoders, _L().mib_decoder_finish_batch(hs, k, outs, st), outs, st)
 
 
 def encode_batch(buffers, options=None, gpus=None):

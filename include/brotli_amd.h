@@ -10,6 +10,8 @@
  *                                                          src/decode/decode.ts:13-65        -> mib_decode
  *   brotliDecodedSize(data)                                src/decode/decode.ts:9-11         -> mib_decoded_size
  *   new BrotliDecoder(opts).update(chunk) / .finish()      (extension: streaming decode)     -> mib_decoder_*
+ *   brotliDecoderUpdateBatch(decoders, chunks) / brotliDecoderFinishBatch(decoders)
+ *                                                          (extension: many sessions a launch) -> mib_decoder_*_batch
  *   EncoderMode {GENERIC 0, TEXT 1, FONT 2}                src/encode/enc-constants.ts:56-60 -> MIB_MODE_*
  *
  * plus batch entry points (host or device-resident buffers) that shard independent buffers
@@ -140,8 +142,31 @@ void mib_decoder_free(mib_decoder *d);
 void mib_decoder_stats(const mib_decoder *d, uint64_t *passes, uint64_t *redecoded);
 /* Diagnostic (tests): a lone session runs the decode kernel's one-stream-per-CU build (65,536
  * LDS table entries); non-zero makes every session launch the four-per-CU build instead (12,224
- * entries, block-type trees in scratch), the one a batch of sessions would get; 0 restores. */
+ * entries, block-type trees in scratch), the one a batch of more sessions than the device has
+ * compute units gets (the batch entry points honour the switch too); 0 restores. */
 void mib_force_decoder_build(int four_per_cu);
+/* Many sessions at once (a service holding many connections): k distinct sessions advance by
+ * one chunk each; a round is ONE decode launch over every session that still has work, and a
+ * call makes as many rounds as its neediest session makes passes.  status[i] / out[i] are what
+ * mib_decoder_update(d[i], ...) / mib_decoder_finish(d[i], ...) alone would have returned, byte
+ * for byte: everything about one stream (a corrupt stream, bytes behind its end, its output
+ * limit, a failed allocation, an earlier error) is that session's status and leaves the others
+ * running.  The sessions may be in any state and have any options; batch and solo calls may be
+ * mixed on one session.  The call itself returns 0, MIB_E_NO_DEVICE, or MIB_E_INVALID_ARG (a NULL
+ * array with k > 0, a NULL handle, NULL data with a size, the same handle twice: checked before
+ * any session is touched).  A call whose chunks are all empty needs no device. */
+int mib_decoder_update_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *out, int *status);
+int mib_decoder_finish_batch(mib_decoder *const *d, size_t k, mib_buf *out, int *status);
+/* Diagnostic (tests): decode launches made by the batch entry points since process start. */
+void mib_decoder_batch_stats(uint64_t *launches);
+/* Diagnostic (scripts/stream_decode_rate.py): host wall time the batch rounds have spent since
+ * process start, ms[0..4] = upload (jobs, heads, move descriptors; the move launch), the
+ * decode launch until it is done, the read-back of jobs and heads, the gather (descriptors and
+ * launch), the download of the span and its cutting into results. */
+void mib_decoder_batch_times(double *ms, int n);
+/* Diagnostic (tests): at most this many blocks per batch launch (0: the default), so a small
+ * batch runs the kernel's job loop more than once per block. */
+void mib_force_decoder_grid(int max_blocks);
 
 /* Batches of independent buffers in host memory; one result (and status) per buffer. */
 int mib_encode_batch(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out, int *status);

@@ -4,6 +4,13 @@ same run; MB/s of output, the ratio to one-shot, device passes and re-decoded ou
 update.  One JSON line.
 
     python scripts/stream_decode_rate.py [--reps 3] [--quality 5]
+
+--sessions K: K sessions, each decoding its own 1 MiB stream (a seed per session) in 64 KiB
+updates, all through decoder_update_batch, and in the same process the same sessions one after
+another through update(); aggregate MB/s of both, the batch's launches and rounds, and one
+round's host wall time by phase.
+
+    python scripts/stream_decode_rate.py --sessions 64 [--out-window 65536] [--solo-cap 64]
 """
 import argparse
 import json
@@ -36,11 +43,95 @@ def stream(comp, chunk):
     return n, updates, d.passes, d.redecoded
 
 
+def _text(seed):
+    return bytes(datagen.enwik_text(1 << 20, seed))
+
+
+def _batch_counters():
+    import ctypes
+    lib = brotli_amd._L()
+    n = ctypes.c_uint64()
+    ms = (ctypes.c_double * 5)()
+    lib.mib_decoder_batch_stats(ctypes.byref(n))
+    lib.mib_decoder_batch_times(ms, 5)
+    return int(n.value), list(ms)
+
+
+def sessions(a):
+    """K sessions, each its own 1 MiB stream (seed 5 + i), in 64 KiB updates: all of them
+    through decoder_update_batch, and (the first --solo-cap of them) one after another through
+    update(), the lone session's path."""
+    k, chunk = a.sessions, 64 << 10
+    opts = {'outWindow': a.out_window} if a.out_window else None
+    # (worker processes make the texts before this process opens the GPU; they never open it)
+    import multiprocessing
+    with multiprocessing.get_context('fork').Pool(min(16, k)) as pool:
+        plains = pool.map(_text, range(5, 5 + k))
+    comps = []
+    for at in range(0, k, 64):
+        comps += brotli_amd.encode_batch(plains[at:at + 64], {'quality': a.quality})
+    total = sum(len(p) for p in plains)
+    steps = max((len(c) + chunk - 1) // chunk for c in comps)
+
+    def run_batch():
+        ds = [brotli_amd.BrotliDecoder(opts) for _ in comps]
+        n0, ms0 = _batch_counters()
+        t0 = time.perf_counter()
+        outs = [[] for _ in comps]
+        for t in range(steps):
+            res = brotli_amd.decoder_update_batch(ds, [c[t * chunk:(t + 1) * chunk] for c in comps])
+            for i, r in enumerate(res):
+                outs[i].append(r)
+        for i, r in enumerate(brotli_amd.decoder_finish_batch(ds)):
+            outs[i].append(r)
+        dt = time.perf_counter() - t0
+        n1, ms1 = _batch_counters()
+        return dt, outs, n1 - n0, [b - x for x, b in zip(ms0, ms1)], max(d.passes for d in ds)
+
+    def run_solo(m):
+        ds = [brotli_amd.BrotliDecoder(opts) for _ in range(m)]
+        t0 = time.perf_counter()
+        outs = []
+        for d, c in zip(ds, comps):
+            got = [d.update(c[at:at + chunk]) for at in range(0, len(c), chunk)]
+            got.append(d.finish())
+            outs.append(got)
+        return time.perf_counter() - t0, outs
+
+    best_b = best_s = None
+    m = min(k, a.solo_cap) if a.solo_cap else k
+    for _ in range(a.reps):   # interleaved: batch, solo, batch, solo
+        rb = run_batch()
+        assert all(b''.join(o) == p for o, p in zip(rb[1], plains))
+        rb = (rb[0], None) + rb[2:]
+        best_b = rb if best_b is None or rb[0] < best_b[0] else best_b
+        ts, so = run_solo(m)
+        assert all(b''.join(o) == p for o, p in zip(so, plains))
+        best_s = ts if best_s is None or ts < best_s else best_s
+    dt, _, launches, ms, rounds = best_b
+    solo_rate = sum(len(p) for p in plains[:m]) / best_s / 1e6
+    names = ('upload_ms', 'launch_ms', 'readback_ms', 'gather_ms', 'download_ms')
+    print(json.dumps({'sessions': k, 'quality': a.quality, 'update_bytes': chunk, 'out_window': a.out_window or (16 << 20),
+                      'updates_per_session': steps, 'batch_MBps': round(total / dt / 1e6, 1),
+                      'solo_sessions_timed': m, 'one_after_another_MBps': round(solo_rate, 2),
+                      'speedup': round(total / dt / 1e6 / solo_rate, 1), 'launches': launches,
+                      'neediest_session_passes': rounds, 'batch_seconds': round(dt, 4),
+                      'per_round': {nm: round(v / max(1, launches), 3) for nm, v in zip(names, ms)},
+                      'host_outside_rounds_ms_per_call': round((1e3 * dt - sum(ms)) / (steps + 1), 3)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--quality', type=int, default=5)
+    ap.add_argument('--sessions', type=int, default=0,
+                    help='K sessions through decoder_update_batch against the same sessions one after another')
+    ap.add_argument('--out-window', type=int, default=0, help='outWindow of the sessions (0: the default, 16 MiB)')
+    ap.add_argument('--solo-cap', type=int, default=0,
+                    help='time at most this many of the K sessions one after another (0: all of them)')
     a = ap.parse_args()
+    if a.sessions:
+        return sessions(a)
     res = {'quality': a.quality, 'cases': []}
     for name, size in (('c4_1MiB', 1 << 20), ('c2_64MiB', 64 << 20)):
         plain = bytes(datagen.enwik_text(size, 5))
