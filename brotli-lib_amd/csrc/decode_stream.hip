@@ -126,14 +126,12 @@ __global__ __launch_bounds__(64) void decode_resume_kernel(StreamJob *jobs, int 
   int32_t *block_trees = BIG ? bt_lds : ctxmap_table + 1100;
   for (int jb = blockIdx.x; jb < njobs; jb += gridDim.x) {
     const StreamJob job = jobs[jb];
-    // A batch launch (heads != null) carries the checkpoint heads beside its jobs, so the host
-    // sends and fetches them in one copy each: the head goes to the session's checkpoint here
-    // and comes back below.  The block's waves share one CU, so the barrier orders the stores.
-    uint64_t *slot = heads ? reinterpret_cast<uint64_t *>(heads + (uint64_t)jb * kStreamCkHead) : nullptr;
-    if (slot) {
-      if (LANE < (int)(kStreamCkHead / 8)) reinterpret_cast<uint64_t *>(job.ck)[LANE] = slot[LANE];
-      __syncthreads();
-    }
+    // A launch carries the checkpoint heads beside its jobs, so the host sends and fetches them
+    // in one copy each: the head goes to the session's checkpoint here and comes back below.
+    // The block's waves share one CU, so the barrier orders the stores.
+    uint64_t *slot = reinterpret_cast<uint64_t *>(heads + (uint64_t)jb * kStreamCkHead);
+    if (LANE < (int)(kStreamCkHead / 8)) reinterpret_cast<uint64_t *>(job.ck)[LANE] = slot[LANE];
+    __syncthreads();
     DecJob dj;
     dj.in = job.in;
     dj.in_len = job.in_len;
@@ -154,7 +152,7 @@ __global__ __launch_bounds__(64) void decode_resume_kernel(StreamJob *jobs, int 
       jobs[jb].out_pos = status == kStreamFinished ? (int64_t)s.pos : status > 0 ? (int64_t)ctl.pos : 0;
     }
     __syncthreads();
-    if (slot && LANE < (int)(kStreamCkHead / 8)) slot[LANE] = reinterpret_cast<const uint64_t *>(job.ck)[LANE];
+    if (LANE < (int)(kStreamCkHead / 8)) slot[LANE] = reinterpret_cast<const uint64_t *>(job.ck)[LANE];
   }
 }
 
@@ -225,13 +223,6 @@ __global__ __launch_bounds__(kMoveThreads) void stream_move_batch_kernel(const M
   for (uint64_t t = u.tile0; t < tiles; t += u.step) copy_tile<kMoveThreads>(d.buf, d.buf + d.src, d.n, t);
 }
 
-// the one-move launch (a lone session's history and input moves): the same walk, the
-// descriptor in the arguments
-__global__ __launch_bounds__(kMoveThreads) void stream_move_kernel(uint8_t *buf, uint64_t src, uint64_t n, uint32_t step) {
-  const uint64_t tiles = tiles_of((uint64_t)(uintptr_t)buf, n, kMoveTile);
-  for (uint64_t t = blockIdx.x; t < tiles; t += step) copy_tile<kMoveThreads>(buf, buf + src, n, t);
-}
-
 // span[dst, dst + n) <- src[0, n) for every descriptor (blockIdx.y), its tiles over blockIdx.x.
 // Sources have any alignment; dst is a multiple of 16 and the span 16-byte aligned.
 __global__ __launch_bounds__(kGatherThreads) void stream_gather_kernel(const GatherDesc *descs, uint8_t *span) {
@@ -242,22 +233,14 @@ __global__ __launch_bounds__(kGatherThreads) void stream_gather_kernel(const Gat
 
 }  // namespace mib
 
+// d_heads: njobs checkpoint heads of kStreamCkHead bytes, which the kernel reads and writes
 extern "C" hipError_t mib_decode_resume_launch(mib::StreamJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
                                                int grid, int per_cu, uint8_t *d_heads, hipStream_t stream) {
+  if (!d_heads) return hipErrorInvalidValue;
   if (per_cu <= 1)
     hipLaunchKernelGGL(mib::decode_resume_kernel<true>, dim3(grid), dim3(64), 0, stream, d_jobs, njobs, d_scratch, per_block, d_heads);
   else
     hipLaunchKernelGGL(mib::decode_resume_kernel<false>, dim3(grid), dim3(64), 0, stream, d_jobs, njobs, d_scratch, per_block, d_heads);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t mib_stream_move_launch(uint8_t *d_buf, uint64_t src, uint64_t n, hipStream_t stream) {
-  if (n == 0 || src == 0) return hipSuccess;
-  const mib::MoveDesc d{d_buf, src, n};
-  std::vector<mib::MoveUnit> units;
-  mib::plan_moves(&d, 1, units);   // (one block when the ranges overlap)
-  const uint32_t grid = (uint32_t)units.size();
-  hipLaunchKernelGGL(mib::stream_move_kernel, dim3(grid), dim3(mib::kMoveThreads), 0, stream, d_buf, src, n, grid);
   return hipGetLastError();
 }
 

@@ -21,10 +21,9 @@
 #include "stream_session.h"
 #include "stream_batch.h"
 
-// (d_heads: null, or one checkpoint head per job, loaded before and stored after the job runs)
+// (d_heads: one checkpoint head per job, loaded before and stored after the job runs)
 extern "C" hipError_t mib_decode_resume_launch(mib::StreamJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
                                                int grid, int per_cu, uint8_t *d_heads, hipStream_t stream);
-extern "C" hipError_t mib_stream_move_launch(uint8_t *d_buf, uint64_t src, uint64_t n, hipStream_t stream);
 extern "C" hipError_t mib_stream_move_batch_launch(const mib::MoveDesc *d_descs, const mib::MoveUnit *d_units, uint32_t n_units,
                                                    hipStream_t stream);
 extern "C" hipError_t mib_stream_gather_launch(const mib::GatherDesc *d_descs, uint32_t k, uint32_t blocks, uint8_t *d_span,
@@ -1297,23 +1296,23 @@ int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status) {
 // slack: stream_session.h) and the pending input (from the oldest byte a resume reads again),
 // and between launches the checkpoint.  update() appends its bytes to the pending input and
 // launches decode_resume_kernel until a launch suspends for input; a launch that stops on the
-// output limit has its bytes copied out and the history moved to the buffer's front first.
+// output limit has its bytes copied out and the history moved to the buffer's front first
+// (decoder_batch_rounds: one loop for a lone session and for k of them).  What a launch needs
+// besides -- decode scratch, its job, the checkpoint's head -- is the context's.
 struct mib_decoder {
   int64_t max_out = -1;
   uint64_t out_window = 0;
   std::vector<uint8_t> dict;          // customDictionary until the device copy exists
   bool has_dict = false;
-  uint8_t *d_dict = nullptr, *d_buf = nullptr, *d_in = nullptr, *d_scratch = nullptr;
+  uint8_t *d_dict = nullptr, *d_buf = nullptr, *d_in = nullptr;
   uint64_t buf_cap = 0, in_cap = 0, in_len = 0;
-  mib::StreamCkpt *d_ck = nullptr;
-  mib::StreamJob *d_job = nullptr;
+  mib::StreamCkpt *d_ck = nullptr;    // the window dump lives here; every launch carries the head beside its job
   mib::StreamCkpt ck;                 // host mirror (its window stays on the device)
   int lgwin = 0;                      // 0: the stream's first byte has not arrived
   uint64_t total_out = 0, passes = 0, redone = 0;   // redone: output bytes decoded twice (behind a checkpoint)
   uint64_t need_len = 0;              // pending bytes the next launch needs at least (0: unknown)
   int error = 0;
   bool finished = false;
-  bool ck_stale = false;              // the device checkpoint's head is behind `ck` (a batch call rebased the input)
   int device = 0;
 };
 
@@ -1326,11 +1325,10 @@ constexpr uint64_t kStreamScratch =
 
 void decoder_release(mib_decoder *d) {
   hipSetDevice(d->device);
-  for (void *p : {(void *)d->d_dict, (void *)d->d_buf, (void *)d->d_in, (void *)d->d_scratch, (void *)d->d_ck, (void *)d->d_job})
+  for (void *p : {(void *)d->d_dict, (void *)d->d_buf, (void *)d->d_in, (void *)d->d_ck})
     if (p) hipFree(p);
-  d->d_dict = d->d_buf = d->d_in = d->d_scratch = nullptr;
+  d->d_dict = d->d_buf = d->d_in = nullptr;
   d->d_ck = nullptr;
-  d->d_job = nullptr;
   d->buf_cap = d->in_cap = d->in_len = 0;
 }
 
@@ -1340,8 +1338,7 @@ int decoder_open(mib_decoder *d, mib_ctx *c, uint8_t first) {
   if (lgwin < 0) return -11;   // the reserved window-bits pattern (engine.ts decodeWindowBits)
   d->lgwin = lgwin;
   d->buf_cap = mib::stream_buf_cap(lgwin, d->out_window);
-  if (hipMalloc((void **)&d->d_buf, d->buf_cap) != hipSuccess || hipMalloc((void **)&d->d_scratch, kStreamScratch) != hipSuccess ||
-      hipMalloc((void **)&d->d_ck, sizeof(mib::StreamCkpt)) != hipSuccess || hipMalloc((void **)&d->d_job, sizeof(mib::StreamJob)) != hipSuccess)
+  if (hipMalloc((void **)&d->d_buf, d->buf_cap) != hipSuccess || hipMalloc((void **)&d->d_ck, sizeof(mib::StreamCkpt)) != hipSuccess)
     return MIB_E_OUT_OF_MEMORY;
   if (d->has_dict) {
     if (hipMalloc((void **)&d->d_dict, d->dict.size() + 16) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
@@ -1375,98 +1372,6 @@ int decoder_reserve(mib_decoder *d, mib_ctx *c, size_t n) {
   return 0;
 }
 
-int decoder_append(mib_decoder *d, mib_ctx *c, const uint8_t *in, size_t n) {
-  int rc0 = decoder_reserve(d, c, n);
-  if (rc0) return rc0;
-  if (n) {
-    const mib::HostPiece up{d->d_in + d->in_len, in, n};
-    int rc = mib::ctx_upload(c, c->stream, &up, 1);
-    if (rc) return rc;
-    d->in_len += n;
-  }
-  return 0;
-}
-
-int decoder_put_ckpt(mib_decoder *d, mib_ctx *c) {
-  HIP_OK(hipMemcpyAsync(d->d_ck, &d->ck, kCkHead, hipMemcpyHostToDevice, c->stream));
-  d->ck_stale = false;
-  return 0;
-}
-
-// launches until one suspends for input, the stream ends or fails; the bytes decoded go to `got`
-int decoder_run(mib_decoder *d, mib_ctx *c, int final, std::vector<uint8_t> &got) {
-  // the last launch stopped in front of a raw or metadata block that is still not whole
-  if (!final && d->in_len < d->need_len) return 0;
-  for (;;) {
-    // the history to the buffer's front: the next launch needs out_window + slack behind pos
-    const uint64_t delta = mib::stream_compact_delta(d->ck.e.pos, d->lgwin);
-    if (delta) {
-      HIP_OK(mib_stream_move_launch(d->d_buf, delta, d->ck.e.pos - delta, c->stream));
-      mib::stream_rebase_output(&d->ck, delta);
-      int rc = decoder_put_ckpt(d, c);
-      if (rc) return rc;
-    } else if (d->ck_stale) {
-      int rc = decoder_put_ckpt(d, c);
-      if (rc) return rc;
-    }
-    const uint64_t start = d->ck.e.pos;
-    mib::StreamJob j;
-    memset(&j, 0, sizeof(j));
-    j.in = d->d_in;
-    j.in_len = d->in_len;
-    j.buf = d->d_buf;
-    j.buf_cap = d->buf_cap;
-    j.out_limit = start + d->out_window;
-    j.dict = d->d_dict;
-    j.dict_len = d->has_dict ? d->dict.size() : 0;
-    j.ck = d->d_ck;
-    j.lgwin = d->lgwin;
-    j.final = final;
-    HIP_OK(hipMemcpyAsync(d->d_job, &j, sizeof(j), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(mib_decode_resume_launch(d->d_job, 1, d->d_scratch, kStreamScratch, 1,
-                                    __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, 1), nullptr,
-                                    c->stream));
-    HIP_OK(hipMemcpyAsync(&j, d->d_job, sizeof(j), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(&d->ck, d->d_ck, kCkHead, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    d->passes++;
-    if (j.status == mib::kStreamNeedInput && j.redone > 0) d->redone += (uint64_t)j.redone;
-    if (j.status < 0) return j.status;
-    if (j.out_pos < (int64_t)start || (uint64_t)j.out_pos > d->buf_cap) return MIB_E_NO_PROGRESS;
-    const uint64_t n = (uint64_t)j.out_pos - start;
-    d->total_out += n;
-    if (d->max_out >= 0 && d->total_out > (uint64_t)d->max_out) return MIB_E_OUTPUT_LIMIT;
-    if (n) {
-      const size_t at = got.size();
-      got.resize(at + n);
-      const mib::HostPiece down{got.data() + at, d->d_buf + start, n};
-      int rc = mib::ctx_download(c, c->stream, &down, 1);
-      if (rc) return rc;
-    }
-    if (j.status == mib::kStreamFinished) {
-      d->finished = true;
-      // bytes behind the stream's end: refused, as one-shot decoding refuses them (-17)
-      return d->in_len > ((d->ck.e.bit + 7) >> 3) ? -17 : 0;
-    }
-    if (j.status == mib::kStreamNeedOutput) continue;   // (the checkpoint is where the launch left)
-    if (j.status != mib::kStreamNeedInput || final) return MIB_E_NO_PROGRESS;
-    d->need_len = j.need_len > 0 ? (uint64_t)j.need_len : 0;
-    break;
-  }
-  // input no resume reads again leaves the front of the pending bytes (once it is worth a move)
-  const uint64_t keep = mib::stream_keep_from(d->ck);
-  if (keep >= (64u << 10) && 2 * keep >= d->in_len) {
-    HIP_OK(mib_stream_move_launch(d->d_in, keep, d->in_len - keep, c->stream));
-    d->in_len -= keep;
-    d->need_len = d->need_len > keep ? d->need_len - keep : 0;
-    mib::stream_rebase_input(&d->ck, keep);
-    int rc = decoder_put_ckpt(d, c);
-    if (rc) return rc;
-    HIP_OK(hipStreamSynchronize(c->stream));
-  }
-  return 0;
-}
-
 int decoder_result(mib_decoder *d, int rc, std::vector<uint8_t> &got, mib_buf *out) {
   if (rc == 0) {
     out->data = mib_buf_alloc(got.size());
@@ -1484,13 +1389,18 @@ int decoder_result(mib_decoder *d, int rc, std::vector<uint8_t> &got, mib_buf *o
   return rc;
 }
 
-// ---------------------------------------------------------------- batches of sessions
-// mib_decoder_update_batch / finish_batch: the sessions of a call advance in rounds, and a round
-// is decoder_run's loop body for every session that still has a launch to make -- with one
-// upload (jobs, checkpoint heads, move descriptors), one move launch, ONE decode launch, one
-// read-back (jobs and heads), one gather launch and one download, however many sessions.
-// A session's job has exactly the parameters its solo launch would have, so its returns, its
-// passes and its redecoded bytes are the solo call's (stream_batch.h holds the planning).
+// ---------------------------------------------------------------- the rounds of a call
+// Every session entry point -- mib_decoder_update / finish are the batch calls with k = 1 --
+// advances its sessions in rounds.  A round, for every session that still has a launch to make:
+// the history moves to the buffer's front if the next launch needs the room, the job is built,
+// ONE decode launch runs all of them, and each session's job and checkpoint head come back to be
+// accounted (passes, redone, total_out against max_out), its new bytes are fetched and its
+// status decides whether it is done, failed, goes into the next round (stopped on the output
+// limit) or leaves to wait for input.  However many sessions, a round is one upload (jobs,
+// checkpoint heads, move descriptors), one move launch, one decode launch, one read-back, one
+// gather launch and one download.  A session's job depends on that session alone, so its
+// returns, its passes and its redecoded bytes do not depend on what else is in the call
+// (stream_batch.h holds the planning).
 uint64_t g_batch_launches = 0;   // mib_decoder_batch_stats
 int g_decoder_grid_cap = 0;      // mib_force_decoder_grid
 double g_batch_ms[5];            // mib_decoder_batch_times: upload, launch, read-back, gather, download
@@ -1498,7 +1408,7 @@ double g_batch_ms[5];            // mib_decoder_batch_times: upload, launch, rea
 struct BatchSlot {
   mib_decoder *d = nullptr;
   int rc = 0;
-  bool run = false;       // has a launch to make in the next round
+  bool run = false;       // has a launch to make in the next round (after the last: an input move to wait for)
   bool suspended = false; // left on kStreamNeedInput: its pending input may be compacted
   uint64_t start = 0, n = 0;
   int status = 0;
@@ -1592,14 +1502,14 @@ int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final) {
     HIP_OK(hipMemcpyAsync(host.data(), c->d_sbatch, heads_at + k * kCkHead, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     const auto t3 = clk::now();
-    // each session's launch, as decoder_run reads it
+    // each session's launch: its pass counts, an error ends the session, its new bytes are
+    // [start, out_pos) and count against max_out (a session over its limit returns none of them)
     for (size_t a = 0; a < k; a++) {
       BatchSlot &s = slots[act[a]];
       mib_decoder *d = s.d;
       mib::StreamJob j;
       memcpy(&j, host.data() + a * sizeof(j), sizeof(j));
       memcpy(&d->ck, host.data() + heads_at + a * kCkHead, kCkHead);
-      d->ck_stale = false;
       d->passes++;
       s.status = j.status;
       s.n = 0;
@@ -1684,8 +1594,8 @@ int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final) {
       moves.push_back(mib::MoveDesc{d->d_in, keep, d->in_len - keep});
       d->in_len -= keep;
       d->need_len = d->need_len > keep ? d->need_len - keep : 0;
-      mib::stream_rebase_input(&d->ck, keep);
-      d->ck_stale = true;   // the next launch brings the head: a batch's with its jobs, a solo one's first
+      mib::stream_rebase_input(&d->ck, keep);   // (the session's next launch brings the rebased head)
+      s.run = true;   // until the move is done: a device failure in it ends this session too
     }
   }
   if (!moves.empty()) {
@@ -1696,6 +1606,7 @@ int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final) {
     HIP_OK(mib_stream_move_batch_launch((const mib::MoveDesc *)c->d_sbatch, (const mib::MoveUnit *)(c->d_sbatch + units_at),
                                         (uint32_t)units.size(), c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
+    for (BatchSlot &s : slots) s.run = false;
   }
   return 0;
 }
@@ -1711,7 +1622,7 @@ int decoder_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *
     std::sort(seen.begin(), seen.end());
     if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return MIB_E_INVALID_ARG;
   }
-  // what each session's solo call would do before it needs the device
+  // a call whose sessions all return without a launch (failed, finished, nothing to add) needs no device
   bool device = false;
   for (size_t i = 0; i < k; i++)
     if (!d[i]->error && !d[i]->finished && (finish || in[i].size)) device = true;
@@ -1806,44 +1717,25 @@ mib_decoder *mib_decoder_new(const mib_dec_opts *o) {
   return d;
 }
 
+// a lone session's calls are the batch calls with k = 1 (`out` is emptied here: a call that
+// finds no device returns before it touches its slots)
 int mib_decoder_update(mib_decoder *d, const uint8_t *in, size_t n, mib_buf *out) {
   if (!d || !out || (!in && n)) return MIB_E_INVALID_ARG;
   out->data = nullptr;
   out->size = 0;
-  if (d->error) return d->error;
-  std::vector<uint8_t> got;
-  if (n == 0) return decoder_result(d, 0, got, out);
-  if (d->finished) return decoder_result(d, -17, got, out);
-  DefaultUse use;
-  mib_ctx *c = default_ctx();
-  if (!c) return MIB_E_NO_DEVICE;
-  hipSetDevice(c->device);
-  d->device = c->device;
-  int rc = 0;
-  if (!d->lgwin) rc = decoder_open(d, c, in[0]);
-  if (!rc) rc = decoder_append(d, c, in, n);
-  if (!rc) rc = decoder_run(d, c, 0, got);
-  return decoder_result(d, rc, got, out);
+  const mib_span s{in, n};
+  int status = 0;
+  const int rc = decoder_batch(&d, &s, 1, out, &status, false);
+  return rc ? rc : status;
 }
 
 int mib_decoder_finish(mib_decoder *d, mib_buf *out) {
   if (!d || !out) return MIB_E_INVALID_ARG;
   out->data = nullptr;
   out->size = 0;
-  if (d->error) return d->error;
-  std::vector<uint8_t> got;
-  if (d->finished) return decoder_result(d, 0, got, out);
-  DefaultUse use;
-  mib_ctx *c = default_ctx();
-  if (!c) return MIB_E_NO_DEVICE;
-  hipSetDevice(c->device);
-  d->device = c->device;
-  int rc = 0;
-  // no byte at all: the decoder reads an empty input's padding, window bits 0 (16) first
-  if (!d->lgwin) rc = decoder_open(d, c, 0);
-  if (!rc) rc = decoder_append(d, c, nullptr, 0);
-  if (!rc) rc = decoder_run(d, c, 1, got);
-  return decoder_result(d, rc, got, out);
+  int status = 0;
+  const int rc = decoder_batch(&d, nullptr, 1, out, &status, true);
+  return rc ? rc : status;
 }
 
 int mib_decoder_is_finished(const mib_decoder *d) { return d && d->finished && !d->error; }

@@ -1,7 +1,8 @@
-// Batches of streaming decoder sessions (mib_decoder_update_batch, DESIGN.md §4d "Batches of
-// sessions"): the descriptors the host and the batch kernels of decode_stream.hip share, and the
-// planning of a round -- which sessions launch, where each session's output lies in the staging
-// span, which block moves which tiles, how large the decode grid is.  Plain C++ (no HIP types):
+// The rounds of the streaming decoder's calls, one session's or many (mib_decoder_update,
+// mib_decoder_update_batch; DESIGN.md §4d "Rounds"): the descriptors the host and the move and
+// gather kernels of decode_stream.hip share, and the planning of a round -- which sessions
+// launch, where each session's output lies in the staging span, which block moves which tiles,
+// how large the decode grid is.  Plain C++ (no HIP types):
 // the planning is exercised by a stand-alone host program under sanitizers
 // (tests/stream_batch_host_main.cpp).
 #pragma once
@@ -78,8 +79,10 @@ inline uint32_t gather_blocks(const uint64_t *len, size_t k) {
 }
 
 // A session launches in the first round of a call unless its last launch stopped in front of a
-// raw or metadata block that is still not whole (decoder_run's first line); later rounds take
-// the sessions whose launch stopped on the output limit.
+// raw or metadata block that is still not whole: that launch reported how many pending bytes
+// the block needs (need_len), and until they are there -- or finish() says no more come -- a
+// launch could only stop at the same place.  Later rounds take the sessions whose launch
+// stopped on the output limit.
 inline bool stream_enters_round(bool final, uint64_t in_len, uint64_t need_len) { return final || in_len >= need_len; }
 
 // The decode launch's grid: a block per job up to cus x per_cu resident waves, and `cap`

@@ -140,10 +140,10 @@ void mib_decoder_free(mib_decoder *d);
  * session has made, and the output bytes it decoded more than once (a launch that runs out of
  * input goes back to its last checkpoint).  Either pointer may be NULL. */
 void mib_decoder_stats(const mib_decoder *d, uint64_t *passes, uint64_t *redecoded);
-/* Diagnostic (tests): a lone session runs the decode kernel's one-stream-per-CU build (65,536
- * LDS table entries); non-zero makes every session launch the four-per-CU build instead (12,224
- * entries, block-type trees in scratch), the one a batch of more sessions than the device has
- * compute units gets (the batch entry points honour the switch too); 0 restores. */
+/* Diagnostic (tests): a call over no more sessions than the device has compute units runs the
+ * decode kernel's one-stream-per-CU build (65,536 LDS table entries); non-zero makes every
+ * launch of the session entry points use the four-per-CU build instead (12,224 entries,
+ * block-type trees in scratch), the one a batch of more sessions gets; 0 restores. */
 void mib_force_decoder_build(int four_per_cu);
 /* Many sessions at once (a service holding many connections): k distinct sessions advance by
  * one chunk each; a round is ONE decode launch over every session that still has work, and a
@@ -157,11 +157,12 @@ void mib_force_decoder_build(int four_per_cu);
  * any session is touched).  A call whose chunks are all empty needs no device. */
 int mib_decoder_update_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *out, int *status);
 int mib_decoder_finish_batch(mib_decoder *const *d, size_t k, mib_buf *out, int *status);
-/* Diagnostic (tests): decode launches made by the batch entry points since process start. */
+/* Diagnostic (tests): decode launches made by the session entry points (mib_decoder_update /
+ * finish and their batch forms) since process start. */
 void mib_decoder_batch_stats(uint64_t *launches);
-/* Diagnostic (scripts/stream_decode_rate.py): host wall time the batch rounds have spent since
- * process start, ms[0..4] = upload (jobs, heads, move descriptors; the move launch), the
- * decode launch until it is done, the read-back of jobs and heads, the gather (descriptors and
+/* Diagnostic (scripts/stream_decode_rate.py): host wall time the rounds of the decode launches
+ * made by the session entry points have spent since process start, ms[0..4] = upload (jobs,
+ * heads, move descriptors; the move launch), the decode launch until it is done, the read-back of jobs and heads, the gather (descriptors and
  * launch), the download of the span and its cutting into results. */
 void mib_decoder_batch_times(double *ms, int n);
 /* Diagnostic (tests): at most this many blocks per batch launch (0: the default), so a small

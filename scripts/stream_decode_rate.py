@@ -60,7 +60,7 @@ def _batch_counters():
 def sessions(a):
     """K sessions, each its own 1 MiB stream (seed 5 + i), in 64 KiB updates: all of them
     through decoder_update_batch, and (the first --solo-cap of them) one after another through
-    update(), the lone session's path."""
+    update(): the same rounds, a session per call."""
     k, chunk = a.sessions, 64 << 10
     opts = {'outWindow': a.out_window} if a.out_window else None
     # (worker processes make the texts before this process opens the GPU; they never open it)

@@ -388,6 +388,31 @@ def test_output_limit():
     assert got == full
 
 
+def test_solo_trace_is_the_parents():
+    """tests/golden/stream_solo_trace.json (scripts/record_stream_trace.py, recorded from the
+    library of the commit it names, the last with a loop of its own for a lone session): every
+    stream of at most 256 KiB compressed, alone through update() / finish() in 4,096-byte chunks
+    and with seeded cuts at outWindow 64 KiB.  What only the host loop determines is the
+    recording's -- the length of every call's return (so, the bytes held back until the next
+    call), passes and redecoded -- and the joined bytes are the oracle's."""
+    with open(os.path.join(G, 'stream_solo_trace.json')) as f:
+        rec = {(c['name'], c['schedule']): c for c in json.load(f)['cases']}
+    n = 0
+    for i, (name, data, exp) in enumerate(_streams()):
+        if len(data) > 256 << 10:
+            continue
+        for schedule, sizes, opts in (('b4096', _cuts_fixed(len(data), 4096), None),
+                                      ('rand', _cuts_random(len(data), 31 * i + len(name)), {'outWindow': WIN})):
+            c = rec.pop((name, schedule))
+            d, outs = _feed(data, sizes, opts)
+            outs.append(d.finish())
+            assert [len(o) for o in outs] == c['lens'], (name, schedule)
+            assert (d.passes, d.redecoded) == (c['passes'], c['redecoded']), (name, schedule)
+            assert b''.join(outs) == exp, (name, schedule)
+            n += 1
+    assert not rec and n == 164   # every recorded case, and the corpus has no stream the recording lacks
+
+
 def test_existing_paths_after_a_session():
     """the default context's state: one-shot and batch decoding after sessions have run, and
     with one still open"""

@@ -182,6 +182,18 @@ def test_one_launch_per_round():
     assert brotli_amd.decoder_finish_batch(ds) == [b''] * len(ds)
 
 
+def test_solo_update_is_a_counted_launch():
+    """a lone session's update() goes through the same rounds: the launch counter rises by exactly
+    that session's passes (several: the stream's output is more than two windows)"""
+    _, data, exp = _by_name('alice29.txt.compressed')
+    d = brotli_amd.BrotliDecoder({'outWindow': WIN})
+    before = _batch_launches()
+    out = d.update(data)
+    made = _batch_launches() - before
+    assert out == exp and d.finished
+    assert d.passes >= 3 and made == d.passes
+
+
 def test_kernel_builds_and_grid_cap():
     """the named synthetic streams as one batch through the four-per-CU build, and with the grid
     capped at 5 blocks so that every block loops over several jobs"""
