@@ -231,6 +231,17 @@ __global__ __launch_bounds__(kGatherThreads) void stream_gather_kernel(const Gat
   for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) copy_tile<kGatherThreads>(span + d.dst, d.src, d.n, t);
 }
 
+// dst[0, n) <- src[0, n) for every descriptor (blockIdx.y), its tiles over blockIdx.x.  Source
+// and destination have any alignment and are pointers of their own, so the tiles are counted
+// over the destination's granules from its misalignment.  Two destinations may share a
+// 16-byte granule: a granule that is not whole inside [0, n) is written byte by byte, by its
+// own descriptor only (copy_tile), so neither touches the other's bytes or anything outside.
+__global__ __launch_bounds__(kGatherThreads) void stream_copy_batch_kernel(const CopyDesc *descs) {
+  const CopyDesc d = descs[blockIdx.y];
+  const uint64_t tiles = tiles_of((uint64_t)(uintptr_t)d.dst, d.n, kGatherTile);
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) copy_tile<kGatherThreads>(d.dst, d.src, d.n, t);
+}
+
 }  // namespace mib
 
 // d_heads: njobs checkpoint heads of kStreamCkHead bytes, which the kernel reads and writes
@@ -257,6 +268,13 @@ extern "C" hipError_t mib_stream_gather_launch(const mib::GatherDesc *d_descs, u
                                                hipStream_t stream) {
   if (k == 0) return hipSuccess;
   hipLaunchKernelGGL(mib::stream_gather_kernel, dim3(blocks, k), dim3(mib::kGatherThreads), 0, stream, d_descs, d_span);
+  return hipGetLastError();
+}
+
+// k descriptors (<= kGatherMaxDescs), `blocks` blocks each (stream_batch.h plan_copies)
+extern "C" hipError_t mib_stream_copy_batch_launch(const mib::CopyDesc *d_descs, uint32_t k, uint32_t blocks, hipStream_t stream) {
+  if (k == 0) return hipSuccess;
+  hipLaunchKernelGGL(mib::stream_copy_batch_kernel, dim3(blocks, k), dim3(mib::kGatherThreads), 0, stream, d_descs);
   return hipGetLastError();
 }
 

@@ -26,6 +26,7 @@ extern "C" hipError_t mib_decode_resume_launch(mib::StreamJob *d_jobs, int njobs
                                                int grid, int per_cu, uint8_t *d_heads, hipStream_t stream);
 extern "C" hipError_t mib_stream_move_batch_launch(const mib::MoveDesc *d_descs, const mib::MoveUnit *d_units, uint32_t n_units,
                                                    hipStream_t stream);
+extern "C" hipError_t mib_stream_copy_batch_launch(const mib::CopyDesc *d_descs, uint32_t k, uint32_t blocks, hipStream_t stream);
 extern "C" hipError_t mib_stream_gather_launch(const mib::GatherDesc *d_descs, uint32_t k, uint32_t blocks, uint8_t *d_span,
                                                hipStream_t stream);
 extern "C" hipError_t mib_decode_stream_init_tables(const int16_t *host_lut);
@@ -1311,6 +1312,11 @@ struct mib_decoder {
   int lgwin = 0;                      // 0: the stream's first byte has not arrived
   uint64_t total_out = 0, passes = 0, redone = 0;   // redone: output bytes decoded twice (behind a checkpoint)
   uint64_t need_len = 0;              // pending bytes the next launch needs at least (0: unknown)
+  // device-resident calls (mib_decoder_update_batch_device): d_buf[deliv, held_to) is decoded and
+  // not yet handed out, and `due` says a launch is owed (input or finish() that has seen no launch
+  // yet, or the last launch left on kStreamNeedOutput) -- both only after a range ran out of room
+  uint64_t deliv = 0, held_to = 0;
+  bool due = false;
   int error = 0;
   bool finished = false;
   int device = 0;
@@ -1330,6 +1336,8 @@ void decoder_release(mib_decoder *d) {
   d->d_dict = d->d_buf = d->d_in = nullptr;
   d->d_ck = nullptr;
   d->buf_cap = d->in_cap = d->in_len = 0;
+  d->deliv = d->held_to = 0;
+  d->due = false;
 }
 
 // the stream's first byte is here: its window sizes the session buffer
@@ -1401,19 +1409,46 @@ int decoder_result(mib_decoder *d, int rc, std::vector<uint8_t> &got, mib_buf *o
 // gather launch and one download.  A session's job depends on that session alone, so its
 // returns, its passes and its redecoded bytes do not depend on what else is in the call
 // (stream_batch.h holds the planning).
+//
+// Delivery.  What a launch decoded is first HELD by its session, d_buf[deliv, held_to), and then
+// delivered: a host call's slot takes everything (gather launch, download, cut into `got`), a
+// device-resident call's slot takes min(held, room left) straight into the caller's range, all
+// slots in one copy launch and nothing through host memory.  Delivery before launch: a session
+// that holds bytes only delivers in a round and gets a job only with nothing held and room left,
+// so the history moves with nothing held, as it always has.  A slot whose range is full leaves
+// the rounds holding the rest, or owing its launch (`due`), for the next call of either kind.
 uint64_t g_batch_launches = 0;   // mib_decoder_batch_stats
 int g_decoder_grid_cap = 0;      // mib_force_decoder_grid
-double g_batch_ms[5];            // mib_decoder_batch_times: upload, launch, read-back, gather, download
+double g_batch_ms[5];            // mib_decoder_batch_times: upload, launch, read-back, gather / delivery, download
 
 struct BatchSlot {
   mib_decoder *d = nullptr;
   int rc = 0;
   bool run = false;       // has a launch to make in the next round (after the last: an input move to wait for)
   bool suspended = false; // left on kStreamNeedInput: its pending input may be compacted
-  uint64_t start = 0, n = 0;
-  int status = 0;
+  uint64_t start = 0;
   std::vector<uint8_t> got;
+  // a device-resident call's slot: where its next byte goes, how much the range still takes,
+  // what it has been given (a host call's slot has no limit and fills `got`)
+  uint8_t *d_dst = nullptr;
+  uint64_t room = mib::kNoRoomLimit, given = 0;
 };
+
+uint64_t held(const mib_decoder *d) { return d->held_to - d->deliv; }
+
+// descriptors to the front of the context's batch buffer (whose content goes) and the copy
+// launches over them (stream_batch.h plan_copies); asynchronous on the context's stream
+int copy_batch(mib_ctx *c, const std::vector<mib::CopyDesc> &cd) {
+  if (cd.empty()) return 0;
+  int rc;
+  if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, cd.size() * sizeof(mib::CopyDesc))) != 0) return rc;
+  HIP_OK(hipMemcpyAsync(c->d_sbatch, cd.data(), cd.size() * sizeof(mib::CopyDesc), hipMemcpyHostToDevice, c->stream));
+  std::vector<mib::CopyLaunch> ls;
+  mib::plan_copies(cd.data(), cd.size(), mib::kGatherMaxDescs, ls);
+  for (const mib::CopyLaunch &l : ls)
+    HIP_OK(mib_stream_copy_batch_launch((const mib::CopyDesc *)c->d_sbatch + l.first, (uint32_t)l.count, l.blocks, c->stream));
+  return 0;
+}
 
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
   return std::chrono::duration<double, std::milli>(b - a).count();
@@ -1430,116 +1465,166 @@ uint64_t stage_moves(const std::vector<mib::MoveDesc> &moves, std::vector<mib::M
   return units_at;
 }
 
-// the rounds of one call over the slots with `run` set; a non-zero return is a device failure
-// that ends every session still in a round
-int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final) {
+// One round's decode launch over the slots `jobs`, each of which holds nothing: the histories
+// move, the jobs go up, ONE launch runs them, jobs and checkpoint heads come back.  Each session
+// then holds its launch's bytes [start, out_pos), and its status says whether it is done, failed,
+// has a further launch to make (`run`) or waits for input.  t[0..3]: the ends of the legs upload,
+// launch and read-back (mib_decoder_batch_times).
+int decoder_launch_round(mib_ctx *c, std::vector<BatchSlot> &slots, const std::vector<size_t> &jobs, int final,
+                         std::chrono::steady_clock::time_point *t) {
   using clk = std::chrono::steady_clock;
-  std::vector<size_t> act;
+  const int cus = (c->device >= 0 && c->device < kMaxDevices && g_dev_cus[c->device] > 0) ? g_dev_cus[c->device] : 256;
+  std::vector<uint8_t> host;
+  std::vector<mib::MoveDesc> moves;
+  std::vector<mib::MoveUnit> units;
+  int rc;
+  const size_t k = jobs.size();
+  // [jobs][heads][move descriptors][move units]: one upload; the first two come back
+  const uint64_t heads_at = mib::stream_heads_offset(k, sizeof(mib::StreamJob));
+  const uint64_t moves_at = (heads_at + k * kCkHead + 15) & ~15ull;
+  host.assign(moves_at, 0);
+  for (size_t a = 0; a < k; a++) {
+    BatchSlot &s = slots[jobs[a]];
+    mib_decoder *d = s.d;
+    // the history to the buffer's front: the next launch needs out_window + slack behind pos
+    const uint64_t delta = mib::stream_compact_delta(d->ck.e.pos, d->lgwin);
+    if (delta) {
+      moves.push_back(mib::MoveDesc{d->d_buf, delta, d->ck.e.pos - delta});
+      mib::stream_rebase_output(&d->ck, delta);
+    }
+    s.start = d->ck.e.pos;
+    d->deliv = d->held_to = s.start;
+    mib::StreamJob j;
+    memset(&j, 0, sizeof(j));
+    j.in = d->d_in;
+    j.in_len = d->in_len;
+    j.buf = d->d_buf;
+    j.buf_cap = d->buf_cap;
+    j.out_limit = mib::stream_out_limit(s.start, d->out_window, s.room);
+    j.dict = d->d_dict;
+    j.dict_len = d->has_dict ? d->dict.size() : 0;
+    j.ck = d->d_ck;
+    j.lgwin = d->lgwin;
+    j.final = final;
+    memcpy(host.data() + a * sizeof(j), &j, sizeof(j));
+    memcpy(host.data() + heads_at + a * kCkHead, &d->ck, kCkHead);
+  }
+  const uint64_t units_at = stage_moves(moves, units, moves_at, host);
+  if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, host.size())) != 0) return rc;
+  const int per_cu = __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, k);
+  const int grid = mib::stream_batch_grid(k, cus, per_cu, __atomic_load_n(&g_decoder_grid_cap, __ATOMIC_RELAXED));
+  c->scratch_trim.need = std::max(c->scratch_trim.need, kStreamScratch * (uint64_t)grid);
+  if ((rc = grow((void **)&c->d_scratch, &c->scratch_bytes, kStreamScratch * (uint64_t)grid)) != 0) return rc;
+  HIP_OK(hipMemcpyAsync(c->d_sbatch, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_OK(mib_stream_move_batch_launch((const mib::MoveDesc *)(c->d_sbatch + moves_at), (const mib::MoveUnit *)(c->d_sbatch + units_at),
+                                      (uint32_t)units.size(), c->stream));
+  t[1] = clk::now();
+  HIP_OK(mib_decode_resume_launch((mib::StreamJob *)c->d_sbatch, (int)k, c->d_scratch, kStreamScratch, grid, per_cu,
+                                  c->d_sbatch + heads_at, c->stream));
+  __atomic_add_fetch(&g_batch_launches, 1, __ATOMIC_RELAXED);
+  // (waiting here, not in the copy, costs nothing -- the copy into pageable memory waits for the
+  // launch anyway -- and lets mib_decoder_batch_times tell the launch from the read-back)
+  HIP_OK(hipStreamSynchronize(c->stream));
+  t[2] = clk::now();
+  HIP_OK(hipMemcpyAsync(host.data(), c->d_sbatch, heads_at + k * kCkHead, hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  t[3] = clk::now();
+  // each session's launch: its pass counts, an error ends the session, its new bytes are
+  // [start, out_pos) and count against max_out (a session over its limit returns none of them)
+  for (size_t a = 0; a < k; a++) {
+    BatchSlot &s = slots[jobs[a]];
+    mib_decoder *d = s.d;
+    mib::StreamJob j;
+    memcpy(&j, host.data() + a * sizeof(j), sizeof(j));
+    memcpy(&d->ck, host.data() + heads_at + a * kCkHead, kCkHead);
+    d->passes++;
+    s.run = false;
+    if (j.status == mib::kStreamNeedInput && j.redone > 0) d->redone += (uint64_t)j.redone;
+    if (j.status < 0) { s.rc = j.status; continue; }
+    if (j.out_pos < (int64_t)s.start || (uint64_t)j.out_pos > d->buf_cap) { s.rc = MIB_E_NO_PROGRESS; continue; }
+    d->total_out += (uint64_t)j.out_pos - s.start;
+    if (d->max_out >= 0 && d->total_out > (uint64_t)d->max_out) { s.rc = MIB_E_OUTPUT_LIMIT; continue; }
+    d->held_to = (uint64_t)j.out_pos;
+    if (j.status == mib::kStreamNeedInput && !final) d->need_len = j.need_len > 0 ? (uint64_t)j.need_len : 0;
+    if (j.status == mib::kStreamFinished) {
+      d->finished = true;
+      // bytes behind the stream's end: refused, as one-shot decoding refuses them (-17)
+      if (d->in_len > ((d->ck.e.bit + 7) >> 3)) s.rc = -17;
+    } else if (j.status == mib::kStreamNeedOutput) {   // (the checkpoint is where the launch left)
+      s.run = true;
+    } else if (j.status != mib::kStreamNeedInput || final) {
+      s.rc = MIB_E_NO_PROGRESS;
+    } else {
+      s.suspended = true;
+    }
+  }
+  return 0;
+}
+
+// the rounds of one call over the slots that have a launch to make (`run`) or hold bytes;
+// to_device: the bytes go to the slots' device ranges (d_dst, room), not to `got`.  A non-zero
+// return is a device failure that ends every session still in a round
+int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final, bool to_device) {
+  using clk = std::chrono::steady_clock;
+  std::vector<size_t> act, jobs, who, next;
   for (size_t i = 0; i < slots.size(); i++) {
     BatchSlot &s = slots[i];
-    if (!s.run) continue;
+    if (s.rc) continue;
     // the last launch stopped in front of a raw or metadata block that is still not whole
-    if (!mib::stream_enters_round(final != 0, s.d->in_len, s.d->need_len)) s.run = false;
-    else act.push_back(i);
+    if (s.run && !mib::stream_enters_round(final != 0, s.d->in_len, s.d->need_len)) s.run = false;
+    if ((s.run || held(s.d)) && s.room > 0) act.push_back(i);
   }
-  const int cus = (c->device >= 0 && c->device < kMaxDevices && g_dev_cus[c->device] > 0) ? g_dev_cus[c->device] : 256;
   std::vector<uint8_t> host, span;
   std::vector<mib::MoveDesc> moves;
   std::vector<mib::MoveUnit> units;
   std::vector<mib::GatherDesc> gd;
+  std::vector<mib::CopyDesc> cd;
   std::vector<uint64_t> len, dst;
   int rc;
   while (!act.empty()) {
-    const auto t0 = clk::now();
-    const size_t k = act.size();
-    // [jobs][heads][move descriptors][move units]: one upload; the first two come back
-    const uint64_t heads_at = mib::stream_heads_offset(k, sizeof(mib::StreamJob));
-    const uint64_t moves_at = (heads_at + k * kCkHead + 15) & ~15ull;
-    host.assign(moves_at, 0);
-    moves.clear();
-    for (size_t a = 0; a < k; a++) {
-      BatchSlot &s = slots[act[a]];
-      mib_decoder *d = s.d;
-      // the history to the buffer's front: the next launch needs out_window + slack behind pos
-      const uint64_t delta = mib::stream_compact_delta(d->ck.e.pos, d->lgwin);
-      if (delta) {
-        moves.push_back(mib::MoveDesc{d->d_buf, delta, d->ck.e.pos - delta});
-        mib::stream_rebase_output(&d->ck, delta);
-      }
-      s.start = d->ck.e.pos;
-      mib::StreamJob j;
-      memset(&j, 0, sizeof(j));
-      j.in = d->d_in;
-      j.in_len = d->in_len;
-      j.buf = d->d_buf;
-      j.buf_cap = d->buf_cap;
-      j.out_limit = s.start + d->out_window;
-      j.dict = d->d_dict;
-      j.dict_len = d->has_dict ? d->dict.size() : 0;
-      j.ck = d->d_ck;
-      j.lgwin = d->lgwin;
-      j.final = final;
-      memcpy(host.data() + a * sizeof(j), &j, sizeof(j));
-      memcpy(host.data() + heads_at + a * kCkHead, &d->ck, kCkHead);
-    }
-    const uint64_t units_at = stage_moves(moves, units, moves_at, host);
-    if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, host.size())) != 0) return rc;
-    const int per_cu = __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, k);
-    const int grid = mib::stream_batch_grid(k, cus, per_cu, __atomic_load_n(&g_decoder_grid_cap, __ATOMIC_RELAXED));
-    c->scratch_trim.need = std::max(c->scratch_trim.need, kStreamScratch * (uint64_t)grid);
-    if ((rc = grow((void **)&c->d_scratch, &c->scratch_bytes, kStreamScratch * (uint64_t)grid)) != 0) return rc;
-    HIP_OK(hipMemcpyAsync(c->d_sbatch, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(mib_stream_move_batch_launch((const mib::MoveDesc *)(c->d_sbatch + moves_at), (const mib::MoveUnit *)(c->d_sbatch + units_at),
-                                        (uint32_t)units.size(), c->stream));
-    const auto t1 = clk::now();
-    HIP_OK(mib_decode_resume_launch((mib::StreamJob *)c->d_sbatch, (int)k, c->d_scratch, kStreamScratch, grid, per_cu,
-                                    c->d_sbatch + heads_at, c->stream));
-    __atomic_add_fetch(&g_batch_launches, 1, __ATOMIC_RELAXED);
-    // (waiting here, not in the copy, costs nothing -- the copy into pageable memory waits for the
-    // launch anyway -- and lets mib_decoder_batch_times tell the launch from the read-back)
-    HIP_OK(hipStreamSynchronize(c->stream));
-    const auto t2 = clk::now();
-    HIP_OK(hipMemcpyAsync(host.data(), c->d_sbatch, heads_at + k * kCkHead, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    const auto t3 = clk::now();
-    // each session's launch: its pass counts, an error ends the session, its new bytes are
-    // [start, out_pos) and count against max_out (a session over its limit returns none of them)
-    for (size_t a = 0; a < k; a++) {
-      BatchSlot &s = slots[act[a]];
-      mib_decoder *d = s.d;
-      mib::StreamJob j;
-      memcpy(&j, host.data() + a * sizeof(j), sizeof(j));
-      memcpy(&d->ck, host.data() + heads_at + a * kCkHead, kCkHead);
-      d->passes++;
-      s.status = j.status;
-      s.n = 0;
-      if (j.status == mib::kStreamNeedInput && j.redone > 0) d->redone += (uint64_t)j.redone;
-      if (j.status < 0) { s.rc = j.status; continue; }
-      if (j.out_pos < (int64_t)s.start || (uint64_t)j.out_pos > d->buf_cap) { s.rc = MIB_E_NO_PROGRESS; continue; }
-      s.n = (uint64_t)j.out_pos - s.start;
-      d->total_out += s.n;
-      if (d->max_out >= 0 && d->total_out > (uint64_t)d->max_out) { s.rc = MIB_E_OUTPUT_LIMIT; s.n = 0; continue; }
-      if (j.status == mib::kStreamNeedInput && !final) d->need_len = j.need_len > 0 ? (uint64_t)j.need_len : 0;
-    }
-    // every session's [start, out_pos) to the staging span, the span down in one copy
-    gd.clear();
+    clk::time_point t[4];
+    t[0] = t[1] = t[2] = t[3] = clk::now();
+    // who launches: the sessions that hold nothing, have room left and a launch to make
+    jobs.clear();
+    for (size_t i : act)
+      if (mib::stream_plans_job(held(slots[i].d), slots[i].room, slots[i].run)) jobs.push_back(i);
+    if (!jobs.empty() && (rc = decoder_launch_round(c, slots, jobs, final, t)) != 0) return rc;
+    // who delivers: every session of the round that holds bytes, min(held, room left) of them
+    who.clear();
     len.clear();
-    std::vector<size_t> who;
-    for (size_t a = 0; a < k; a++)
-      if (slots[act[a]].n) {
-        who.push_back(act[a]);
-        len.push_back(slots[act[a]].n);
+    for (size_t i : act) {
+      const BatchSlot &s = slots[i];
+      const uint64_t n = s.rc ? 0 : mib::deliver_len(held(s.d), s.room);
+      if (n) {
+        who.push_back(i);
+        len.push_back(n);
       }
-    auto t4 = t3, t5 = t3;
-    if (!who.empty()) {
+    }
+    auto t4 = t[3], t5 = t[3];
+    if (!who.empty() && to_device) {
+      // one copy launch into the callers' ranges; nothing comes down
+      cd.clear();
+      for (size_t g = 0; g < who.size(); g++) {
+        BatchSlot &s = slots[who[g]];
+        cd.push_back(mib::CopyDesc{s.d->d_buf + s.d->deliv, s.d_dst, len[g]});
+        s.d_dst += len[g];
+        s.room -= len[g];
+        s.given += len[g];
+      }
+      if ((rc = copy_batch(c, cd)) != 0) return rc;
+      HIP_OK(hipStreamSynchronize(c->stream));
+      t4 = t5 = clk::now();
+    } else if (!who.empty()) {
+      // every session's bytes to the staging span, the span down in one copy
+      gd.clear();
       dst.resize(who.size());
       const uint64_t total = mib::plan_gather(len.data(), len.size(), dst.data());
       for (size_t g = 0; g < who.size(); g++)
-        gd.push_back(mib::GatherDesc{slots[who[g]].d->d_buf + slots[who[g]].start, len[g], dst[g]});
+        gd.push_back(mib::GatherDesc{slots[who[g]].d->d_buf + slots[who[g]].d->deliv, len[g], dst[g]});
       c->sspan_trim.need = std::max(c->sspan_trim.need, total);
       if ((rc = grow((void **)&c->d_sspan, &c->sspan_bytes, total)) != 0) return rc;
-      // (the descriptors take the place of the jobs, which are read: never more of them, never larger)
-      static_assert(sizeof(mib::GatherDesc) <= sizeof(mib::StreamJob), "gather descriptors fit where the jobs were");
+      // (the descriptors take the place of the jobs, which are read)
+      if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, gd.size() * sizeof(mib::GatherDesc))) != 0) return rc;
       HIP_OK(hipMemcpyAsync(c->d_sbatch, gd.data(), gd.size() * sizeof(mib::GatherDesc), hipMemcpyHostToDevice, c->stream));
       for (size_t g0 = 0; g0 < gd.size(); g0 += mib::kGatherMaxDescs) {
         const size_t g1 = std::min(gd.size(), g0 + mib::kGatherMaxDescs);
@@ -1556,33 +1641,23 @@ int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final) {
       }
       t5 = clk::now();
     }
-    g_batch_ms[0] += ms_between(t0, t1);
-    g_batch_ms[1] += ms_between(t1, t2);
-    g_batch_ms[2] += ms_between(t2, t3);
-    g_batch_ms[3] += ms_between(t3, t4);
+    for (size_t g = 0; g < who.size(); g++) slots[who[g]].d->deliv += len[g];
+    g_batch_ms[0] += ms_between(t[0], t[1]);
+    g_batch_ms[1] += ms_between(t[1], t[2]);
+    g_batch_ms[2] += ms_between(t[2], t[3]);
+    g_batch_ms[3] += ms_between(t[3], t4);
     g_batch_ms[4] += ms_between(t4, t5);
-    // who goes on
-    std::vector<size_t> next;
-    for (size_t a = 0; a < k; a++) {
-      BatchSlot &s = slots[act[a]];
-      mib_decoder *d = s.d;
-      s.run = false;
-      if (s.rc) continue;
-      if (s.status == mib::kStreamFinished) {
-        d->finished = true;
-        // bytes behind the stream's end: refused, as one-shot decoding refuses them (-17)
-        if (d->in_len > ((d->ck.e.bit + 7) >> 3)) s.rc = -17;
-      } else if (s.status == mib::kStreamNeedOutput) {   // (the checkpoint is where the launch left)
-        s.run = true;
-        next.push_back(act[a]);
-      } else if (s.status != mib::kStreamNeedInput || final) {
-        s.rc = MIB_E_NO_PROGRESS;
-      } else {
-        s.suspended = true;
-      }
+    // who goes on: a launch to make or bytes held, and room for them
+    next.clear();
+    for (size_t i : act) {
+      const BatchSlot &s = slots[i];
+      if (!s.rc && (s.run || held(s.d)) && s.room > 0) next.push_back(i);
     }
     act.swap(next);
   }
+  // a slot whose range ran out before its launch could be made owes it to the next call
+  for (BatchSlot &s : slots)
+    if (!s.d->error) s.d->due = s.run && !s.rc;
   // input no resume reads again leaves the front of the pending bytes (once it is worth a move):
   // every session's move in one launch
   moves.clear();
@@ -1611,21 +1686,46 @@ int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final) {
   return 0;
 }
 
-// update (in != null) or finish (in == null) of k sessions
-int decoder_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *out, int *status, bool finish) {
-  if (k == 0) return 0;
-  if (!d || !out || !status || (!finish && !in)) return MIB_E_INVALID_ARG;
-  for (size_t i = 0; i < k; i++)
-    if (!d[i] || (!finish && !in[i].data && in[i].size)) return MIB_E_INVALID_ARG;
-  {
-    std::vector<const mib_decoder *> seen(d, d + k);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return MIB_E_INVALID_ARG;
+// Where a call's chunks come from and where its bytes go: host memory (in, out) or, for the
+// device-resident calls, ranges of two device buffers given by host offset arrays.
+struct BatchIo {
+  const mib_span *in = nullptr;
+  mib_buf *out = nullptr;
+  bool device = false;
+  const uint8_t *d_in = nullptr;
+  const uint64_t *in_offsets = nullptr;
+  uint8_t *d_out = nullptr;
+  const uint64_t *out_offsets = nullptr;
+  uint64_t *out_sizes = nullptr;
+  size_t chunk(size_t i, bool finish) const {
+    return finish ? 0 : device ? (size_t)(in_offsets[i + 1] - in_offsets[i]) : in[i].size;
   }
-  // a call whose sessions all return without a launch (failed, finished, nothing to add) needs no device
+};
+
+// The first byte of each of the chunks `open` (slots whose session has not seen a byte yet): its
+// window bits size the session buffer on the host.  One copy launch collects them behind its
+// descriptors, one read-back brings them.
+int fetch_first_bytes(mib_ctx *c, const BatchIo &io, const std::vector<size_t> &open, std::vector<uint8_t> &first) {
+  first.assign(open.size(), 0);
+  if (open.empty()) return 0;
+  const uint64_t at = (open.size() * sizeof(mib::CopyDesc) + 15) & ~15ull;
+  int rc;
+  if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, at + open.size())) != 0) return rc;
+  std::vector<mib::CopyDesc> cd;
+  for (size_t j = 0; j < open.size(); j++) cd.push_back(mib::CopyDesc{io.d_in + io.in_offsets[open[j]], c->d_sbatch + at + j, 1});
+  if ((rc = copy_batch(c, cd)) != 0) return rc;
+  HIP_OK(hipMemcpyAsync(first.data(), c->d_sbatch + at, open.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// update or finish of k sessions, already checked (decoder_batch_check)
+int decoder_batch(mib_decoder *const *d, const BatchIo &io, size_t k, int *status, bool finish) {
+  // a call whose sessions all return without a launch or a delivery (failed, finished, nothing to
+  // add, nothing held) needs no device
   bool device = false;
   for (size_t i = 0; i < k; i++)
-    if (!d[i]->error && !d[i]->finished && (finish || in[i].size)) device = true;
+    if (!d[i]->error && (held(d[i]) || d[i]->due || (!d[i]->finished && (finish || io.chunk(i, finish))))) device = true;
   struct Hold {   // (the default context for the whole call, taken only when a session needs the device)
     bool on = false;
     ~Hold() { if (on) mib_default_lock(0); }
@@ -1640,36 +1740,112 @@ int decoder_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *
   }
   std::vector<BatchSlot> slots(k);
   std::vector<mib::HostPiece> up;
+  std::vector<mib::CopyDesc> app;
+  std::vector<size_t> open;
+  std::vector<uint8_t> first;
+  int rc = 0;
+  if (io.device && !finish) {
+    for (size_t i = 0; i < k; i++)
+      if (!d[i]->error && !d[i]->finished && !d[i]->lgwin && io.chunk(i, finish)) open.push_back(i);
+    if (!open.empty()) rc = fetch_first_bytes(c, io, open, first);
+  }
+  size_t opened = 0;
   for (size_t i = 0; i < k; i++) {
     BatchSlot &s = slots[i];
     s.d = d[i];
-    out[i].data = nullptr;
-    out[i].size = 0;
     status[i] = 0;
-    if (d[i]->error) continue;
-    if (finish ? d[i]->finished : in[i].size == 0) continue;   // returns 0 and nothing
-    if (d[i]->finished) { s.rc = -17; continue; }
-    d[i]->device = c->device;
-    // no byte at all (finish): the decoder reads an empty input's padding, window bits 0 (16) first
-    if (!d[i]->lgwin) s.rc = decoder_open(d[i], c, finish ? 0 : in[i].data[0]);
-    if (!s.rc) s.rc = decoder_reserve(d[i], c, finish ? 0 : in[i].size);
-    if (s.rc) continue;
-    if (!finish) {
-      up.push_back(mib::HostPiece{d[i]->d_in + d[i]->in_len, in[i].data, in[i].size});
-      d[i]->in_len += in[i].size;
+    if (io.device) {
+      io.out_sizes[i] = 0;
+      s.d_dst = io.d_out + io.out_offsets[i];
+      s.room = io.out_offsets[i + 1] - io.out_offsets[i];
+    } else {
+      io.out[i].data = nullptr;
+      io.out[i].size = 0;
     }
-    s.run = true;
+    if (d[i]->error) continue;
+    const size_t n = io.chunk(i, finish);
+    // bytes held or a launch owed (a device-resident call ran out of room): this call goes on there
+    const bool pending = held(d[i]) || d[i]->due;
+    if (!pending && (finish ? d[i]->finished : n == 0)) continue;   // returns 0 and nothing
+    if (d[i]->finished) {
+      if (n) s.rc = -17;
+      continue;   // (what it holds is delivered)
+    }
+    d[i]->device = c->device;
+    if (finish || n) {
+      if (rc) { s.rc = rc; continue; }   // the first bytes did not come: the call fails below
+      // no byte at all (finish): the decoder reads an empty input's padding, window bits 0 (16) first
+      if (!d[i]->lgwin) s.rc = decoder_open(d[i], c, finish ? 0 : io.device ? first[opened++] : io.in[i].data[0]);
+      if (!s.rc) s.rc = decoder_reserve(d[i], c, n);
+      if (s.rc) continue;
+      if (n) {
+        if (io.device) app.push_back(mib::CopyDesc{io.d_in + io.in_offsets[i], d[i]->d_in + d[i]->in_len, n});
+        else up.push_back(mib::HostPiece{d[i]->d_in + d[i]->in_len, io.in[i].data, n});
+        d[i]->in_len += n;
+      }
+      s.run = true;
+    } else {
+      s.run = d[i]->due;
+    }
   }
-  int rc = 0;
-  if (!up.empty()) rc = mib::ctx_upload(c, c->stream, up.data(), up.size());
-  if (!rc && c) rc = decoder_batch_rounds(c, slots, finish ? 1 : 0);
+  // every slot's chunk behind its session's pending input: one copy launch, or the host's pieces
+  if (!rc && !app.empty()) rc = copy_batch(c, app);
+  if (!rc && !up.empty()) rc = mib::ctx_upload(c, c->stream, up.data(), up.size());
+  if (!rc && c) rc = decoder_batch_rounds(c, slots, finish ? 1 : 0, io.device);
   for (size_t i = 0; i < k; i++) {
     BatchSlot &s = slots[i];
     if (d[i]->error) { status[i] = d[i]->error; continue; }
-    if (rc && s.run) s.rc = rc;   // a device failure ends the sessions that still had a launch to make
-    status[i] = decoder_result(d[i], s.rc, s.got, &out[i]);
+    if (rc && (s.run || held(d[i]))) s.rc = rc;   // a device failure ends the sessions that still had work
+    if (!io.device) {
+      status[i] = decoder_result(d[i], s.rc, s.got, &io.out[i]);
+    } else if (s.rc) {
+      mib_buf none{nullptr, 0};
+      status[i] = decoder_result(d[i], s.rc, s.got, &none);
+      io.out_sizes[i] = none.size;   // (MIB_E_OUTPUT_LIMIT: the total, as in the host call)
+    } else {
+      io.out_sizes[i] = s.given;
+      status[i] = mib::stream_more_output(held(d[i]), s.room, d[i]->due) ? MIB_DEC_MORE_OUTPUT : 0;
+    }
   }
   return 0;
+}
+
+// what every batch call checks before it touches a session
+int decoder_batch_check(mib_decoder *const *d, size_t k) {
+  if (!d) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++)
+    if (!d[i]) return MIB_E_INVALID_ARG;
+  std::vector<const mib_decoder *> seen(d, d + k);
+  std::sort(seen.begin(), seen.end());
+  return std::adjacent_find(seen.begin(), seen.end()) != seen.end() ? MIB_E_INVALID_ARG : 0;
+}
+
+int decoder_batch_host(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *out, int *status, bool finish) {
+  if (k == 0) return 0;
+  if (!out || !status || (!finish && !in) || decoder_batch_check(d, k)) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++)
+    if (!finish && !in[i].data && in[i].size) return MIB_E_INVALID_ARG;
+  BatchIo io;
+  io.in = in;
+  io.out = out;
+  return decoder_batch(d, io, k, status, finish);
+}
+
+int decoder_batch_device(mib_decoder *const *d, const uint8_t *d_in, const uint64_t *in_offsets, size_t k, uint8_t *d_out,
+                         const uint64_t *out_offsets, uint64_t *out_sizes, int *status, bool finish) {
+  if (k == 0) return 0;
+  if (!out_offsets || !out_sizes || !status || (!finish && !in_offsets) || decoder_batch_check(d, k)) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++)
+    if (out_offsets[i + 1] < out_offsets[i] || (!finish && in_offsets[i + 1] < in_offsets[i])) return MIB_E_INVALID_ARG;
+  if ((!d_out && out_offsets[k] > out_offsets[0]) || (!finish && !d_in && in_offsets[k] > in_offsets[0])) return MIB_E_INVALID_ARG;
+  BatchIo io;
+  io.device = true;
+  io.d_in = d_in;
+  io.in_offsets = in_offsets;
+  io.d_out = d_out;
+  io.out_offsets = out_offsets;
+  io.out_sizes = out_sizes;
+  return decoder_batch(d, io, k, status, finish);
 }
 }  // namespace
 
@@ -1677,11 +1853,42 @@ extern "C" {
 
 int mib_decoder_update_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *out, int *status) {
   if (k && !in) return MIB_E_INVALID_ARG;
-  return decoder_batch(d, in, k, out, status, false);
+  return decoder_batch_host(d, in, k, out, status, false);
 }
 
 int mib_decoder_finish_batch(mib_decoder *const *d, size_t k, mib_buf *out, int *status) {
-  return decoder_batch(d, nullptr, k, out, status, true);
+  return decoder_batch_host(d, nullptr, k, out, status, true);
+}
+
+int mib_decoder_update_batch_device(mib_decoder *const *d, const uint8_t *d_in, const uint64_t *in_offsets, size_t k,
+                                    uint8_t *d_out, const uint64_t *out_offsets, uint64_t *out_sizes, int *status) {
+  return decoder_batch_device(d, d_in, in_offsets, k, d_out, out_offsets, out_sizes, status, false);
+}
+
+int mib_decoder_finish_batch_device(mib_decoder *const *d, size_t k, uint8_t *d_out, const uint64_t *out_offsets,
+                                    uint64_t *out_sizes, int *status) {
+  return decoder_batch_device(d, nullptr, nullptr, k, d_out, out_offsets, out_sizes, status, true);
+}
+
+uint64_t mib_decoder_held_output(const mib_decoder *d) { return d && !d->error ? d->held_to - d->deliv : 0; }
+
+// Diagnostic: the copy kernel alone, over host arrays of device pointers
+int mib_debug_copy_batch(const uint8_t *const *d_src, uint8_t *const *d_dst, const uint64_t *n, size_t k) {
+  if (k == 0) return 0;
+  if (!d_src || !d_dst || !n) return MIB_E_INVALID_ARG;
+  std::vector<mib::CopyDesc> cd;
+  for (size_t i = 0; i < k; i++) {
+    if (n[i] && (!d_src[i] || !d_dst[i])) return MIB_E_INVALID_ARG;
+    cd.push_back(mib::CopyDesc{d_src[i], d_dst[i], n[i]});
+  }
+  DefaultUse use;
+  mib_ctx *c = default_ctx();
+  if (!c) return MIB_E_NO_DEVICE;
+  hipSetDevice(c->device);
+  const int rc = copy_batch(c, cd);
+  if (rc) return rc;
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 void mib_decoder_batch_stats(uint64_t *launches) {
@@ -1725,7 +1932,7 @@ int mib_decoder_update(mib_decoder *d, const uint8_t *in, size_t n, mib_buf *out
   out->size = 0;
   const mib_span s{in, n};
   int status = 0;
-  const int rc = decoder_batch(&d, &s, 1, out, &status, false);
+  const int rc = decoder_batch_host(&d, &s, 1, out, &status, false);
   return rc ? rc : status;
 }
 
@@ -1734,7 +1941,7 @@ int mib_decoder_finish(mib_decoder *d, mib_buf *out) {
   out->data = nullptr;
   out->size = 0;
   int status = 0;
-  const int rc = decoder_batch(&d, nullptr, 1, out, &status, true);
+  const int rc = decoder_batch_host(&d, nullptr, 1, out, &status, true);
   return rc ? rc : status;
 }
 

@@ -2,7 +2,8 @@
 // mib_decoder_update_batch; DESIGN.md §4d "Rounds"): the descriptors the host and the move and
 // gather kernels of decode_stream.hip share, and the planning of a round -- which sessions
 // launch, where each session's output lies in the staging span, which block moves which tiles,
-// how large the decode grid is.  Plain C++ (no HIP types):
+// how large the decode grid is, and for the device-resident calls how much a slot delivers,
+// what it goes on holding and when it launches.  Plain C++ (no HIP types):
 // the planning is exercised by a stand-alone host program under sanitizers
 // (tests/stream_batch_host_main.cpp).
 #pragma once
@@ -95,6 +96,56 @@ inline int stream_batch_grid(size_t jobs, int cus, int per_cu, int cap) {
   if (jobs < g) g = jobs;
   if (cap > 0 && (uint64_t)cap < g) g = (uint64_t)cap;
   return (int)g;
+}
+
+// ---------------------------------------------------------------- device-resident batches
+// (mib_decoder_update_batch_device, DESIGN.md §4d "Device-resident batches")
+// dst[0, n) <- src[0, n), both of any alignment and pointers of their own: a slot's chunk goes
+// to its session's pending input, a session's decoded bytes go to the caller's range
+struct CopyDesc {
+  const uint8_t *src;
+  uint8_t *dst;
+  uint64_t n;
+};
+constexpr uint64_t kNoRoomLimit = ~0ull;   // a host call's slot: its results grow as needed
+
+// A session between launches may hold decoded bytes the caller has not fetched, held = pos -
+// deliv of its buffer, and may owe a launch (`due`: new input or finish() it has not launched
+// for, or its last launch left on the output limit).  Delivery before launch: while it holds
+// bytes it only delivers, so its history moves (stream_compact_delta) and its positions are
+// rebased with nothing held, exactly as for a session that never holds anything.
+constexpr uint64_t deliver_len(uint64_t held, uint64_t room) { return held < room ? held : room; }
+// a session gets a job in a round only with nothing held and room left
+constexpr bool stream_plans_job(uint64_t held, uint64_t room, bool due) { return due && held == 0 && room > 0; }
+// ... and that job's output limit: no further than the range has room (kNoRoomLimit: the window)
+constexpr uint64_t stream_out_limit(uint64_t start, uint64_t out_window, uint64_t room) {
+  return start + (room < out_window ? room : out_window);
+}
+// a slot leaves its call on MIB_DEC_MORE_OUTPUT exactly when its range is full and work remains
+constexpr bool stream_more_output(uint64_t held, uint64_t room, bool due) { return room == 0 && (held > 0 || due); }
+
+// blocks per descriptor (the grid's x extent) of a copy launch: the most tiles any of its
+// descriptors has over its destination's granules, kGatherSpread at most
+inline uint32_t copy_blocks(const CopyDesc *d, size_t k) {
+  uint64_t most = 1;
+  for (size_t i = 0; i < k; i++) {
+    const uint64_t t = tiles_of((uint64_t)(uintptr_t)d[i].dst, d[i].n, kGatherTile);
+    if (t > most) most = t;
+  }
+  return (uint32_t)(most < kGatherSpread ? most : kGatherSpread);
+}
+// One copy launch: the descriptors [first, first + count), `blocks` blocks each.
+struct CopyLaunch {
+  size_t first, count;
+  uint32_t blocks;
+};
+// k descriptors in launches of at most `max_descs` (kGatherMaxDescs: the grid's y extent)
+inline void plan_copies(const CopyDesc *d, size_t k, size_t max_descs, std::vector<CopyLaunch> &launches) {
+  launches.clear();
+  for (size_t g0 = 0; g0 < k; g0 += max_descs) {
+    const size_t n = k - g0 < max_descs ? k - g0 : max_descs;
+    launches.push_back(CopyLaunch{g0, n, copy_blocks(d + g0, n)});
+  }
 }
 
 // The round's read-back array: k jobs, then k checkpoint heads (the bytes of a StreamCkpt in

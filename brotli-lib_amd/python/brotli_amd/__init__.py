@@ -18,7 +18,7 @@ import os
 
 __all__ = ['brotliEncode', 'BrotliEncoder', 'brotliDecode', 'BrotliDecoder', 'brotliDecodedSize', 'EncoderMode', 'BrotliError',
            'encode_batch', 'decode_batch', 'encoder_update_batch', 'decoder_update_batch', 'decoder_finish_batch',
-           'DeviceContext', 'library_path']
+           'decoder_update_batch_device', 'decoder_finish_batch_device', 'MORE_OUTPUT', 'DeviceContext', 'library_path']
 
 _PKG = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # BROTLI_AMD_LIB: an instrumented build of the same library (timing experiments only)
@@ -155,6 +155,16 @@ def _L():
             lib.mib_decoder_batch_times.restype = None
             lib.mib_force_decoder_grid.argtypes = [ctypes.c_int]
             lib.mib_force_decoder_grid.restype = None
+        if hasattr(lib, 'mib_decoder_update_batch_device'):
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            lib.mib_decoder_update_batch_device.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, u64p, ctypes.c_size_t,
+                                                            ctypes.c_void_p, u64p, u64p, ctypes.POINTER(ctypes.c_int)]
+            lib.mib_decoder_finish_batch_device.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_void_p,
+                                                            u64p, u64p, ctypes.POINTER(ctypes.c_int)]
+            lib.mib_decoder_held_output.argtypes = [ctypes.c_void_p]
+            lib.mib_decoder_held_output.restype = ctypes.c_uint64
+            lib.mib_debug_copy_batch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), u64p,
+                                                 ctypes.c_size_t]
         lib.mib_encode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
                                          ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_decode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Buf),
@@ -402,6 +412,11 @@ class BrotliDecoder:
         """diagnostic: output bytes decoded more than once so far"""
         return self._stats()[1]
 
+    @property
+    def held_output(self):
+        """decoded bytes not yet handed out (a device-resident call's range was full)"""
+        return int(_L().mib_decoder_held_output(self._h))
+
     def __del__(self):
         if getattr(self, '_h', None):
             _L().mib_decoder_free(self._h)
@@ -444,6 +459,57 @@ def decoder_finish_batch(decoders):
     outs = (_Buf * k)()
     st = (ctypes.c_int * k)()
     return _decoder_batch_results(decoders, _L().mib_decoder_finish_batch(hs, k, outs, st), outs, st)
+
+
+MORE_OUTPUT = 1   # MIB_DEC_MORE_OUTPUT: the slot's output range is full, the session has more
+
+
+def _device_offsets(what, offsets, k):
+    if len(offsets) != k + 1:
+        raise ValueError('%s: %d decoders need %d offsets, got %d' % (what, k, k + 1, len(offsets)))
+    return (ctypes.c_uint64 * (k + 1))(*offsets)
+
+
+def decoder_update_batch_device(decoders, d_in, in_offsets, d_out, out_offsets):
+    """decoder_update_batch with the chunks and the decoded bytes in device memory
+    (mib_decoder_update_batch_device): d_in / d_out are raw device pointers (tensor.data_ptr()) on
+    the default device, session i's chunk is d_in[in_offsets[i]:in_offsets[i+1]] and its bytes
+    go to d_out[out_offsets[i]:out_offsets[i+1]].  Returns (sizes, statuses): per slot the bytes
+    written and 0, MORE_OUTPUT (the range is full and the session has more: call again, empty
+    chunks will do) or the session's negative error code -- a value, not raised."""
+    k = len(decoders)
+    ioff = _device_offsets('decoder_update_batch_device', in_offsets, k)
+    ooff = _device_offsets('decoder_update_batch_device', out_offsets, k)
+    hs = (ctypes.c_void_p * k)(*[d._h for d in decoders])
+    sizes = (ctypes.c_uint64 * k)()
+    st = (ctypes.c_int * k)()
+    rc = _L().mib_decoder_update_batch_device(hs, d_in, ioff, k, d_out, ooff, sizes, st)
+    if rc:
+        raise _err(rc)
+    return list(sizes), list(st)
+
+
+def decoder_finish_batch_device(decoders, d_out, out_offsets):
+    """decoder_finish_batch into device memory (mib_decoder_finish_batch_device); returns
+    (sizes, statuses) as decoder_update_batch_device does."""
+    k = len(decoders)
+    ooff = _device_offsets('decoder_finish_batch_device', out_offsets, k)
+    hs = (ctypes.c_void_p * k)(*[d._h for d in decoders])
+    sizes = (ctypes.c_uint64 * k)()
+    st = (ctypes.c_int * k)()
+    rc = _L().mib_decoder_finish_batch_device(hs, k, d_out, ooff, sizes, st)
+    if rc:
+        raise _err(rc)
+    return list(sizes), list(st)
+
+
+def debug_copy_batch(srcs, dsts, sizes):
+    """Diagnostic (tests): the device calls' copy kernel alone (mib_debug_copy_batch): copy i moves
+    sizes[i] bytes from the device address srcs[i] to the device address dsts[i]."""
+    k = len(sizes)
+    rc = _L().mib_debug_copy_batch((ctypes.c_void_p * k)(*srcs), (ctypes.c_void_p * k)(*dsts), (ctypes.c_uint64 * k)(*sizes), k)
+    if rc:
+        raise _err(rc)
 
 
 def encode_batch(buffers, options=None, gpus=None):

@@ -12,6 +12,7 @@
  *   new BrotliDecoder(opts).update(chunk) / .finish()      (extension: streaming decode)     -> mib_decoder_*
  *   brotliDecoderUpdateBatch(decoders, chunks) / brotliDecoderFinishBatch(decoders)
  *                                                          (extension: many sessions a launch) -> mib_decoder_*_batch
+ *   (C and Python only: the same with chunks and output in device memory)                        -> mib_decoder_*_batch_device
  *   EncoderMode {GENERIC 0, TEXT 1, FONT 2}                src/encode/enc-constants.ts:56-60 -> MIB_MODE_*
  *
  * plus batch entry points (host or device-resident buffers) that shard independent buffers
@@ -157,13 +158,43 @@ void mib_force_decoder_build(int four_per_cu);
  * any session is touched).  A call whose chunks are all empty needs no device. */
 int mib_decoder_update_batch(mib_decoder *const *d, const mib_span *in, size_t k, mib_buf *out, int *status);
 int mib_decoder_finish_batch(mib_decoder *const *d, size_t k, mib_buf *out, int *status);
+/* The same batches with the chunks and the decoded bytes in device memory (DESIGN.md 4d
+ * "Device-resident batches"): nothing of either passes through host memory.  d_in / d_out are
+ * device pointers on the default context's device (where the sessions live); in_offsets,
+ * out_offsets (k + 1 entries), out_sizes and status (k entries) are host arrays, in the shape
+ * of mib_ctx_decode.  Session i's chunk is d_in[in_offsets[i], in_offsets[i+1]); its bytes go
+ * to d_out + out_offsets[i], room out_offsets[i+1] - out_offsets[i].  Offsets have any
+ * alignment and room may be 0; the ranges must not overlap each other or a session's memory
+ * (the 16-byte granules that hold a chunk's first and last byte are read whole).  Synchronous on
+ * the default context's stream: the caller's writes to d_in are complete before the call, d_out
+ * is complete on return.  Returns as mib_decoder_update_batch (also MIB_E_INVALID_ARG for a
+ * decreasing offset, or a NULL buffer whose offsets span bytes).  Per slot:
+ *   status 0                   out_sizes[i] bytes were written, all that the input so far
+ *                              determines; while no slot runs out of room, byte for byte what
+ *                              the host call returns for the same chunks
+ *   MIB_DEC_MORE_OUTPUT        the range was filled (out_sizes[i] == room) and the session has
+ *                              more: decoded bytes it holds (mib_decoder_held_output) or a launch
+ *                              it still has to make.  Call again; an empty chunk will do
+ *   < 0                        the host call's code; out_sizes[i] 0 (MIB_E_OUTPUT_LIMIT: the total)
+ * Bytes of a range behind out_sizes[i] are unspecified; none outside the range is written.
+ * Host and device calls may be mixed on a session: a host call first returns what is held. */
+#define MIB_DEC_MORE_OUTPUT 1
+int mib_decoder_update_batch_device(mib_decoder *const *d, const uint8_t *d_in, const uint64_t *in_offsets, size_t k,
+                                    uint8_t *d_out, const uint64_t *out_offsets, uint64_t *out_sizes, int *status);
+int mib_decoder_finish_batch_device(mib_decoder *const *d, size_t k, uint8_t *d_out, const uint64_t *out_offsets,
+                                    uint64_t *out_sizes, int *status);
+uint64_t mib_decoder_held_output(const mib_decoder *d);   /* decoded bytes not yet handed out (0 for NULL) */
+/* Diagnostic (tests): the device calls' copy kernel alone, one call over k copies
+ * d_dst[i][0, n[i]) <- d_src[i][0, n[i]); host arrays of device pointers of any alignment. */
+int mib_debug_copy_batch(const uint8_t *const *d_src, uint8_t *const *d_dst, const uint64_t *n, size_t k);
 /* Diagnostic (tests): decode launches made by the session entry points (mib_decoder_update /
  * finish and their batch forms) since process start. */
 void mib_decoder_batch_stats(uint64_t *launches);
 /* Diagnostic (scripts/stream_decode_rate.py): host wall time the rounds of the decode launches
  * made by the session entry points have spent since process start, ms[0..4] = upload (jobs,
  * heads, move descriptors; the move launch), the decode launch until it is done, the read-back of jobs and heads, the gather (descriptors and
- * launch), the download of the span and its cutting into results. */
+ * launch; a device-resident call: its delivery launch), the download of the span and its cutting
+ * into results (a device-resident call adds nothing here). */
 void mib_decoder_batch_times(double *ms, int n);
 /* Diagnostic (tests): at most this many blocks per batch launch (0: the default), so a small
  * batch runs the kernel's job loop more than once per block. */

@@ -11,6 +11,10 @@ another through update(); aggregate MB/s of both, the batch's launches and round
 round's host wall time by phase.
 
     python scripts/stream_decode_rate.py --sessions 64 [--out-window 65536] [--solo-cap 64]
+
+--device (with --sessions): the same sessions and updates through decoder_update_batch_device as
+well, chunks and output in torch tensors, interleaved with the host batch in the same process;
+adds a "device" entry with its MB/s, launches and a round's phases (the download leg stays 0).
 """
 import argparse
 import json
@@ -98,26 +102,80 @@ def sessions(a):
             outs.append(got)
         return time.perf_counter() - t0, outs
 
-    best_b = best_s = None
+    if a.device:
+        # the chunks resident in HBM, step by step back to back (a call's chunks are one run of
+        # d_in); every call writes into the same k ranges of `room` bytes, which hold a whole
+        # stream, so no slot ever reports MORE_OUTPUT
+        import torch
+        room = 1 << 20
+        step_at, flat = [], bytearray()
+        for t in range(steps):
+            offs = [len(flat)]
+            for c in comps:
+                flat += c[t * chunk:(t + 1) * chunk]
+                offs.append(len(flat))
+            step_at.append(offs)
+        d_in = torch.frombuffer(flat, dtype=torch.uint8).to('cuda')
+        d_out = torch.empty(k * room, dtype=torch.uint8, device='cuda')
+        out_offs = [i * room for i in range(k + 1)]
+        torch.cuda.synchronize()
+
+    def run_device(verify):
+        """the same sessions and updates through the device calls; verify: every call's bytes are
+        fetched and returned (not a timed run)"""
+        ds = [brotli_amd.BrotliDecoder(opts) for _ in comps]
+        n0, ms0 = _batch_counters()
+        t0 = time.perf_counter()
+        outs = [[] for _ in comps]
+        total_out = 0
+        for t in range(steps + 1):
+            if t < steps:
+                sizes, st = brotli_amd.decoder_update_batch_device(ds, d_in.data_ptr(), step_at[t], d_out.data_ptr(), out_offs)
+            else:
+                sizes, st = brotli_amd.decoder_finish_batch_device(ds, d_out.data_ptr(), out_offs)
+            assert not any(st), st
+            total_out += sum(sizes)
+            if verify:
+                for i, n in enumerate(sizes):
+                    outs[i].append(d_out[i * room:i * room + n].cpu().numpy().tobytes())
+        dt = time.perf_counter() - t0
+        n1, ms1 = _batch_counters()
+        assert total_out == total
+        return dt, outs, n1 - n0, [b - x for x, b in zip(ms0, ms1)], max(d.passes for d in ds)
+
+    best_b = best_s = best_d = None
     m = min(k, a.solo_cap) if a.solo_cap else k
-    for _ in range(a.reps):   # interleaved: batch, solo, batch, solo
+    if a.device:
+        rd = run_device(True)
+        assert all(b''.join(o) == p for o, p in zip(rd[1], plains))
+    for _ in range(a.reps):   # interleaved: batch, (device,) solo, batch, (device,) solo
         rb = run_batch()
         assert all(b''.join(o) == p for o, p in zip(rb[1], plains))
         rb = (rb[0], None) + rb[2:]
         best_b = rb if best_b is None or rb[0] < best_b[0] else best_b
+        if a.device:
+            rd = run_device(False)
+            best_d = rd if best_d is None or rd[0] < best_d[0] else best_d
         ts, so = run_solo(m)
         assert all(b''.join(o) == p for o, p in zip(so, plains))
         best_s = ts if best_s is None or ts < best_s else best_s
     dt, _, launches, ms, rounds = best_b
     solo_rate = sum(len(p) for p in plains[:m]) / best_s / 1e6
     names = ('upload_ms', 'launch_ms', 'readback_ms', 'gather_ms', 'download_ms')
-    print(json.dumps({'sessions': k, 'quality': a.quality, 'update_bytes': chunk, 'out_window': a.out_window or (16 << 20),
-                      'updates_per_session': steps, 'batch_MBps': round(total / dt / 1e6, 1),
-                      'solo_sessions_timed': m, 'one_after_another_MBps': round(solo_rate, 2),
-                      'speedup': round(total / dt / 1e6 / solo_rate, 1), 'launches': launches,
-                      'neediest_session_passes': rounds, 'batch_seconds': round(dt, 4),
-                      'per_round': {nm: round(v / max(1, launches), 3) for nm, v in zip(names, ms)},
-                      'host_outside_rounds_ms_per_call': round((1e3 * dt - sum(ms)) / (steps + 1), 3)}))
+    res = {'sessions': k, 'quality': a.quality, 'update_bytes': chunk, 'out_window': a.out_window or (16 << 20),
+           'updates_per_session': steps, 'batch_MBps': round(total / dt / 1e6, 1),
+           'solo_sessions_timed': m, 'one_after_another_MBps': round(solo_rate, 2),
+           'speedup': round(total / dt / 1e6 / solo_rate, 1), 'launches': launches,
+           'neediest_session_passes': rounds, 'batch_seconds': round(dt, 4),
+           'per_round': {nm: round(v / max(1, launches), 3) for nm, v in zip(names, ms)},
+           'host_outside_rounds_ms_per_call': round((1e3 * dt - sum(ms)) / (steps + 1), 3)}
+    if a.device:
+        ddt, _, dlaunches, dms, drounds = best_d
+        res['device'] = {'MBps': round(total / ddt / 1e6, 1), 'against_batch': round(dt / ddt, 3), 'launches': dlaunches,
+                         'neediest_session_passes': drounds, 'seconds': round(ddt, 4),
+                         'per_round': {nm: round(v / max(1, dlaunches), 3) for nm, v in zip(names, dms)},
+                         'host_outside_rounds_ms_per_call': round((1e3 * ddt - sum(dms)) / (steps + 1), 3)}
+    print(json.dumps(res))
 
 
 def main():
@@ -129,6 +187,9 @@ def main():
     ap.add_argument('--out-window', type=int, default=0, help='outWindow of the sessions (0: the default, 16 MiB)')
     ap.add_argument('--solo-cap', type=int, default=0,
                     help='time at most this many of the K sessions one after another (0: all of them)')
+    ap.add_argument('--device', action='store_true',
+                    help='with --sessions: the same sessions and updates through decoder_update_batch_device too '
+                         '(chunks and output in torch tensors), interleaved with the host batch')
     a = ap.parse_args()
     if a.sessions:
         return sessions(a)
