@@ -58,5 +58,8 @@ struct DecJob {
 constexpr int kDecodeBlock = 64;                    // one wave per stream
 constexpr uint64_t kDecodeTableInts = 256u * (1 + 630) + 256u * (1 + 1080) + 256u * (1 + 1080) + 64;
 constexpr uint64_t kDecodeCtxBytes = 256u * 64 + 256u * 4 + 256;
+// a decode block's scratch as the kernels carve it: tables, context bytes, distance extra bits
+// and offsets, the context-map table, the block trees (the host sizes its allocations by this)
+constexpr uint64_t kDecodeScratchBytes = kDecodeTableInts * 4 + kDecodeCtxBytes + 1152 + 1152 * 4 + 1100 * 4 + 3092 * 4;
 
 }  // namespace mib

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(64) void decode_resume_kernel(StreamJob *jobs, int 
   }
 }
 
-// ---------------------------------------------------------------- moves and gathers (stream_batch.h)
+// ---------------------------------------------------------------- moves and copies (stream_batch.h)
 // 16 source bytes of any alignment: the two aligned vectors they lie in, shifted together.
 // Only called for 16 bytes that all belong to the source, so the second vector (read when the
 // address is not aligned) holds the last of them and lies in the same allocation.
@@ -223,14 +223,6 @@ __global__ __launch_bounds__(kMoveThreads) void stream_move_batch_kernel(const M
   for (uint64_t t = u.tile0; t < tiles; t += u.step) copy_tile<kMoveThreads>(d.buf, d.buf + d.src, d.n, t);
 }
 
-// span[dst, dst + n) <- src[0, n) for every descriptor (blockIdx.y), its tiles over blockIdx.x.
-// Sources have any alignment; dst is a multiple of 16 and the span 16-byte aligned.
-__global__ __launch_bounds__(kGatherThreads) void stream_gather_kernel(const GatherDesc *descs, uint8_t *span) {
-  const GatherDesc d = descs[blockIdx.y];
-  const uint64_t tiles = tiles_of(0, d.n, kGatherTile);
-  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) copy_tile<kGatherThreads>(span + d.dst, d.src, d.n, t);
-}
-
 // dst[0, n) <- src[0, n) for every descriptor (blockIdx.y), its tiles over blockIdx.x.  Source
 // and destination have any alignment and are pointers of their own, so the tiles are counted
 // over the destination's granules from its misalignment.  Two destinations may share a
@@ -260,14 +252,6 @@ extern "C" hipError_t mib_stream_move_batch_launch(const mib::MoveDesc *d_descs,
                                                    hipStream_t stream) {
   if (n_units == 0) return hipSuccess;
   hipLaunchKernelGGL(mib::stream_move_batch_kernel, dim3(n_units), dim3(mib::kMoveThreads), 0, stream, d_descs, d_units);
-  return hipGetLastError();
-}
-
-// k descriptors (<= kGatherMaxDescs), `blocks` blocks each (stream_batch.h gather_blocks)
-extern "C" hipError_t mib_stream_gather_launch(const mib::GatherDesc *d_descs, uint32_t k, uint32_t blocks, uint8_t *d_span,
-                                               hipStream_t stream) {
-  if (k == 0) return hipSuccess;
-  hipLaunchKernelGGL(mib::stream_gather_kernel, dim3(blocks, k), dim3(mib::kGatherThreads), 0, stream, d_descs, d_span);
   return hipGetLastError();
 }
 

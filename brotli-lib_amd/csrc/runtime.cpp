@@ -13,6 +13,7 @@
 #include <mutex>
 #include <string>
 #include <chrono>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -20,6 +21,7 @@
 #include "parts.h"
 #include "stream_session.h"
 #include "stream_batch.h"
+#include "stream_rounds.h"
 
 // (d_heads: one checkpoint head per job, loaded before and stored after the job runs)
 extern "C" hipError_t mib_decode_resume_launch(mib::StreamJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
@@ -27,8 +29,6 @@ extern "C" hipError_t mib_decode_resume_launch(mib::StreamJob *d_jobs, int njobs
 extern "C" hipError_t mib_stream_move_batch_launch(const mib::MoveDesc *d_descs, const mib::MoveUnit *d_units, uint32_t n_units,
                                                    hipStream_t stream);
 extern "C" hipError_t mib_stream_copy_batch_launch(const mib::CopyDesc *d_descs, uint32_t k, uint32_t blocks, hipStream_t stream);
-extern "C" hipError_t mib_stream_gather_launch(const mib::GatherDesc *d_descs, uint32_t k, uint32_t blocks, uint8_t *d_span,
-                                               hipStream_t stream);
 extern "C" hipError_t mib_decode_stream_init_tables(const int16_t *host_lut);
 extern "C" hipError_t mib_decode_parts_launch(mib::DecJob *d_jobs, int njobs, uint8_t *d_scratch, uint64_t per_block,
                                               unsigned *d_ticket, int grid, int per_cu, hipStream_t stream);
@@ -332,7 +332,7 @@ struct mib_ctx {
   uint8_t *d_parts = nullptr;
   uint64_t parts_bytes = 0;
   // batches of decoder sessions (mib_decoder_update_batch): a round's jobs, checkpoint heads and
-  // move / gather descriptors, and the span the sessions' output is gathered into
+  // move / copy descriptors, and the staging span a host call's output is copied into
   uint8_t *d_sbatch = nullptr;
   uint64_t sbatch_bytes = 0;
   uint8_t *d_sspan = nullptr;
@@ -912,7 +912,7 @@ static int decode_jobs(mib_ctx *c, std::vector<mib::DecJob> &jobs, hipStream_t s
   for (auto &j : jobs) max_log = std::max(max_log, j.max_ring_log);
   uint64_t ring_bytes = ((uint64_t)1 << max_log) + 37 + 256;
   ring_bytes = (ring_bytes + 255) & ~(uint64_t)255;
-  uint64_t per_block = ring_bytes + mib::kDecodeTableInts * 4 + mib::kDecodeCtxBytes + 1152 + 1152 * 4 + 1100 * 4 + 3092 * 4;   // ... ctx-map table, block trees
+  uint64_t per_block = ring_bytes + mib::kDecodeScratchBytes;
   per_block = (per_block + 255) & ~(uint64_t)255;
   // (MIB_DEC_GRID: experiment knob, a smaller persistent grid -- fewer decoder waves per CU)
   static const size_t grid_cap = mib::knob("MIB_DEC_GRID") ? (size_t)std::max(1, atoi(mib::knob("MIB_DEC_GRID"))) : 2048;
@@ -1014,7 +1014,7 @@ static int decode_parts(mib_ctx *c, const std::vector<PartStream> &ps, std::vect
       jobs.push_back(j);
     }
   }
-  uint64_t per_block = mib::kDecodeTableInts * 4 + mib::kDecodeCtxBytes + 1152 + 1152 * 4 + 1100 * 4 + 3092 * 4;
+  uint64_t per_block = mib::kDecodeScratchBytes;
   per_block = (per_block + 255) & ~(uint64_t)255;
   static const size_t grid_cap = mib::knob("MIB_PART_GRID") ? (size_t)std::max(1, atoi(mib::knob("MIB_PART_GRID"))) : 2048;
   const int grid = (int)std::min<size_t>(nj, grid_cap);
@@ -1298,27 +1298,14 @@ int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status) {
 // and between launches the checkpoint.  update() appends its bytes to the pending input and
 // launches decode_resume_kernel until a launch suspends for input; a launch that stops on the
 // output limit has its bytes copied out and the history moved to the buffer's front first
-// (decoder_batch_rounds: one loop for a lone session and for k of them).  What a launch needs
-// besides -- decode scratch, its job, the checkpoint's head -- is the context's.
-struct mib_decoder {
-  int64_t max_out = -1;
-  uint64_t out_window = 0;
+// (mib::stream_rounds, which decides everything over the StreamSession part below).  What a
+// launch needs besides -- decode scratch, its job, the checkpoint's head -- is the context's.
+struct mib_decoder : mib::StreamSession {
   std::vector<uint8_t> dict;          // customDictionary until the device copy exists
   bool has_dict = false;
   uint8_t *d_dict = nullptr, *d_buf = nullptr, *d_in = nullptr;
-  uint64_t buf_cap = 0, in_cap = 0, in_len = 0;
+  uint64_t in_cap = 0;
   mib::StreamCkpt *d_ck = nullptr;    // the window dump lives here; every launch carries the head beside its job
-  mib::StreamCkpt ck;                 // host mirror (its window stays on the device)
-  int lgwin = 0;                      // 0: the stream's first byte has not arrived
-  uint64_t total_out = 0, passes = 0, redone = 0;   // redone: output bytes decoded twice (behind a checkpoint)
-  uint64_t need_len = 0;              // pending bytes the next launch needs at least (0: unknown)
-  // device-resident calls (mib_decoder_update_batch_device): d_buf[deliv, held_to) is decoded and
-  // not yet handed out, and `due` says a launch is owed (input or finish() that has seen no launch
-  // yet, or the last launch left on kStreamNeedOutput) -- both only after a range ran out of room
-  uint64_t deliv = 0, held_to = 0;
-  bool due = false;
-  int error = 0;
-  bool finished = false;
   int device = 0;
 };
 
@@ -1326,8 +1313,7 @@ namespace {
 int g_force_small_decoder = 0;   // mib_force_decoder_build
 constexpr size_t kCkHead = mib::kStreamCkHead;
 static_assert(kCkHead == offsetof(mib::StreamCkpt, win), "the checkpoint head ends where the window starts");
-constexpr uint64_t kStreamScratch =
-    (mib::kDecodeTableInts * 4 + mib::kDecodeCtxBytes + 1152 + 1152 * 4 + 1100 * 4 + 3092 * 4 + 255) & ~(uint64_t)255;
+constexpr uint64_t kStreamScratch = (mib::kDecodeScratchBytes + 255) & ~(uint64_t)255;
 
 void decoder_release(mib_decoder *d) {
   hipSetDevice(d->device);
@@ -1398,43 +1384,13 @@ int decoder_result(mib_decoder *d, int rc, std::vector<uint8_t> &got, mib_buf *o
 }
 
 // ---------------------------------------------------------------- the rounds of a call
-// Every session entry point -- mib_decoder_update / finish are the batch calls with k = 1 --
-// advances its sessions in rounds.  A round, for every session that still has a launch to make:
-// the history moves to the buffer's front if the next launch needs the room, the job is built,
-// ONE decode launch runs all of them, and each session's job and checkpoint head come back to be
-// accounted (passes, redone, total_out against max_out), its new bytes are fetched and its
-// status decides whether it is done, failed, goes into the next round (stopped on the output
-// limit) or leaves to wait for input.  However many sessions, a round is one upload (jobs,
-// checkpoint heads, move descriptors), one move launch, one decode launch, one read-back, one
-// gather launch and one download.  A session's job depends on that session alone, so its
-// returns, its passes and its redecoded bytes do not depend on what else is in the call
-// (stream_batch.h holds the planning).
-//
-// Delivery.  What a launch decoded is first HELD by its session, d_buf[deliv, held_to), and then
-// delivered: a host call's slot takes everything (gather launch, download, cut into `got`), a
-// device-resident call's slot takes min(held, room left) straight into the caller's range, all
-// slots in one copy launch and nothing through host memory.  Delivery before launch: a session
-// that holds bytes only delivers in a round and gets a job only with nothing held and room left,
-// so the history moves with nothing held, as it always has.  A slot whose range is full leaves
-// the rounds holding the rest, or owing its launch (`due`), for the next call of either kind.
+// This file's part of mib::stream_rounds (RoundsDev below).  However many sessions, a round is one
+// upload (jobs, checkpoint heads, move descriptors), one move launch, one decode launch, one
+// read-back, and for what the sessions then deliver ONE copy launch -- into the callers' device
+// ranges, or into the staging span, which comes down in one copy.
 uint64_t g_batch_launches = 0;   // mib_decoder_batch_stats
 int g_decoder_grid_cap = 0;      // mib_force_decoder_grid
-double g_batch_ms[5];            // mib_decoder_batch_times: upload, launch, read-back, gather / delivery, download
-
-struct BatchSlot {
-  mib_decoder *d = nullptr;
-  int rc = 0;
-  bool run = false;       // has a launch to make in the next round (after the last: an input move to wait for)
-  bool suspended = false; // left on kStreamNeedInput: its pending input may be compacted
-  uint64_t start = 0;
-  std::vector<uint8_t> got;
-  // a device-resident call's slot: where its next byte goes, how much the range still takes,
-  // what it has been given (a host call's slot has no limit and fills `got`)
-  uint8_t *d_dst = nullptr;
-  uint64_t room = mib::kNoRoomLimit, given = 0;
-};
-
-uint64_t held(const mib_decoder *d) { return d->held_to - d->deliv; }
+double g_batch_ms[5];            // mib_decoder_batch_times: upload, launch, read-back, delivery launch, download
 
 // descriptors to the front of the context's batch buffer (whose content goes) and the copy
 // launches over them (stream_batch.h plan_copies); asynchronous on the context's stream
@@ -1454,238 +1410,6 @@ double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_c
   return std::chrono::duration<double, std::milli>(b - a).count();
 }
 
-// the moves' descriptors at host[at] and their blocks (plan_moves) behind them; returns where the blocks start
-uint64_t stage_moves(const std::vector<mib::MoveDesc> &moves, std::vector<mib::MoveUnit> &units, uint64_t at,
-                     std::vector<uint8_t> &host) {
-  mib::plan_moves(moves.data(), moves.size(), units);
-  const uint64_t units_at = (at + moves.size() * sizeof(mib::MoveDesc) + 15) & ~15ull;
-  host.resize(units_at + units.size() * sizeof(mib::MoveUnit));
-  if (!moves.empty()) memcpy(host.data() + at, moves.data(), moves.size() * sizeof(mib::MoveDesc));
-  if (!units.empty()) memcpy(host.data() + units_at, units.data(), units.size() * sizeof(mib::MoveUnit));
-  return units_at;
-}
-
-// One round's decode launch over the slots `jobs`, each of which holds nothing: the histories
-// move, the jobs go up, ONE launch runs them, jobs and checkpoint heads come back.  Each session
-// then holds its launch's bytes [start, out_pos), and its status says whether it is done, failed,
-// has a further launch to make (`run`) or waits for input.  t[0..3]: the ends of the legs upload,
-// launch and read-back (mib_decoder_batch_times).
-int decoder_launch_round(mib_ctx *c, std::vector<BatchSlot> &slots, const std::vector<size_t> &jobs, int final,
-                         std::chrono::steady_clock::time_point *t) {
-  using clk = std::chrono::steady_clock;
-  const int cus = (c->device >= 0 && c->device < kMaxDevices && g_dev_cus[c->device] > 0) ? g_dev_cus[c->device] : 256;
-  std::vector<uint8_t> host;
-  std::vector<mib::MoveDesc> moves;
-  std::vector<mib::MoveUnit> units;
-  int rc;
-  const size_t k = jobs.size();
-  // [jobs][heads][move descriptors][move units]: one upload; the first two come back
-  const uint64_t heads_at = mib::stream_heads_offset(k, sizeof(mib::StreamJob));
-  const uint64_t moves_at = (heads_at + k * kCkHead + 15) & ~15ull;
-  host.assign(moves_at, 0);
-  for (size_t a = 0; a < k; a++) {
-    BatchSlot &s = slots[jobs[a]];
-    mib_decoder *d = s.d;
-    // the history to the buffer's front: the next launch needs out_window + slack behind pos
-    const uint64_t delta = mib::stream_compact_delta(d->ck.e.pos, d->lgwin);
-    if (delta) {
-      moves.push_back(mib::MoveDesc{d->d_buf, delta, d->ck.e.pos - delta});
-      mib::stream_rebase_output(&d->ck, delta);
-    }
-    s.start = d->ck.e.pos;
-    d->deliv = d->held_to = s.start;
-    mib::StreamJob j;
-    memset(&j, 0, sizeof(j));
-    j.in = d->d_in;
-    j.in_len = d->in_len;
-    j.buf = d->d_buf;
-    j.buf_cap = d->buf_cap;
-    j.out_limit = mib::stream_out_limit(s.start, d->out_window, s.room);
-    j.dict = d->d_dict;
-    j.dict_len = d->has_dict ? d->dict.size() : 0;
-    j.ck = d->d_ck;
-    j.lgwin = d->lgwin;
-    j.final = final;
-    memcpy(host.data() + a * sizeof(j), &j, sizeof(j));
-    memcpy(host.data() + heads_at + a * kCkHead, &d->ck, kCkHead);
-  }
-  const uint64_t units_at = stage_moves(moves, units, moves_at, host);
-  if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, host.size())) != 0) return rc;
-  const int per_cu = __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, k);
-  const int grid = mib::stream_batch_grid(k, cus, per_cu, __atomic_load_n(&g_decoder_grid_cap, __ATOMIC_RELAXED));
-  c->scratch_trim.need = std::max(c->scratch_trim.need, kStreamScratch * (uint64_t)grid);
-  if ((rc = grow((void **)&c->d_scratch, &c->scratch_bytes, kStreamScratch * (uint64_t)grid)) != 0) return rc;
-  HIP_OK(hipMemcpyAsync(c->d_sbatch, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_OK(mib_stream_move_batch_launch((const mib::MoveDesc *)(c->d_sbatch + moves_at), (const mib::MoveUnit *)(c->d_sbatch + units_at),
-                                      (uint32_t)units.size(), c->stream));
-  t[1] = clk::now();
-  HIP_OK(mib_decode_resume_launch((mib::StreamJob *)c->d_sbatch, (int)k, c->d_scratch, kStreamScratch, grid, per_cu,
-                                  c->d_sbatch + heads_at, c->stream));
-  __atomic_add_fetch(&g_batch_launches, 1, __ATOMIC_RELAXED);
-  // (waiting here, not in the copy, costs nothing -- the copy into pageable memory waits for the
-  // launch anyway -- and lets mib_decoder_batch_times tell the launch from the read-back)
-  HIP_OK(hipStreamSynchronize(c->stream));
-  t[2] = clk::now();
-  HIP_OK(hipMemcpyAsync(host.data(), c->d_sbatch, heads_at + k * kCkHead, hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  t[3] = clk::now();
-  // each session's launch: its pass counts, an error ends the session, its new bytes are
-  // [start, out_pos) and count against max_out (a session over its limit returns none of them)
-  for (size_t a = 0; a < k; a++) {
-    BatchSlot &s = slots[jobs[a]];
-    mib_decoder *d = s.d;
-    mib::StreamJob j;
-    memcpy(&j, host.data() + a * sizeof(j), sizeof(j));
-    memcpy(&d->ck, host.data() + heads_at + a * kCkHead, kCkHead);
-    d->passes++;
-    s.run = false;
-    if (j.status == mib::kStreamNeedInput && j.redone > 0) d->redone += (uint64_t)j.redone;
-    if (j.status < 0) { s.rc = j.status; continue; }
-    if (j.out_pos < (int64_t)s.start || (uint64_t)j.out_pos > d->buf_cap) { s.rc = MIB_E_NO_PROGRESS; continue; }
-    d->total_out += (uint64_t)j.out_pos - s.start;
-    if (d->max_out >= 0 && d->total_out > (uint64_t)d->max_out) { s.rc = MIB_E_OUTPUT_LIMIT; continue; }
-    d->held_to = (uint64_t)j.out_pos;
-    if (j.status == mib::kStreamNeedInput && !final) d->need_len = j.need_len > 0 ? (uint64_t)j.need_len : 0;
-    if (j.status == mib::kStreamFinished) {
-      d->finished = true;
-      // bytes behind the stream's end: refused, as one-shot decoding refuses them (-17)
-      if (d->in_len > ((d->ck.e.bit + 7) >> 3)) s.rc = -17;
-    } else if (j.status == mib::kStreamNeedOutput) {   // (the checkpoint is where the launch left)
-      s.run = true;
-    } else if (j.status != mib::kStreamNeedInput || final) {
-      s.rc = MIB_E_NO_PROGRESS;
-    } else {
-      s.suspended = true;
-    }
-  }
-  return 0;
-}
-
-// the rounds of one call over the slots that have a launch to make (`run`) or hold bytes;
-// to_device: the bytes go to the slots' device ranges (d_dst, room), not to `got`.  A non-zero
-// return is a device failure that ends every session still in a round
-int decoder_batch_rounds(mib_ctx *c, std::vector<BatchSlot> &slots, int final, bool to_device) {
-  using clk = std::chrono::steady_clock;
-  std::vector<size_t> act, jobs, who, next;
-  for (size_t i = 0; i < slots.size(); i++) {
-    BatchSlot &s = slots[i];
-    if (s.rc) continue;
-    // the last launch stopped in front of a raw or metadata block that is still not whole
-    if (s.run && !mib::stream_enters_round(final != 0, s.d->in_len, s.d->need_len)) s.run = false;
-    if ((s.run || held(s.d)) && s.room > 0) act.push_back(i);
-  }
-  std::vector<uint8_t> host, span;
-  std::vector<mib::MoveDesc> moves;
-  std::vector<mib::MoveUnit> units;
-  std::vector<mib::GatherDesc> gd;
-  std::vector<mib::CopyDesc> cd;
-  std::vector<uint64_t> len, dst;
-  int rc;
-  while (!act.empty()) {
-    clk::time_point t[4];
-    t[0] = t[1] = t[2] = t[3] = clk::now();
-    // who launches: the sessions that hold nothing, have room left and a launch to make
-    jobs.clear();
-    for (size_t i : act)
-      if (mib::stream_plans_job(held(slots[i].d), slots[i].room, slots[i].run)) jobs.push_back(i);
-    if (!jobs.empty() && (rc = decoder_launch_round(c, slots, jobs, final, t)) != 0) return rc;
-    // who delivers: every session of the round that holds bytes, min(held, room left) of them
-    who.clear();
-    len.clear();
-    for (size_t i : act) {
-      const BatchSlot &s = slots[i];
-      const uint64_t n = s.rc ? 0 : mib::deliver_len(held(s.d), s.room);
-      if (n) {
-        who.push_back(i);
-        len.push_back(n);
-      }
-    }
-    auto t4 = t[3], t5 = t[3];
-    if (!who.empty() && to_device) {
-      // one copy launch into the callers' ranges; nothing comes down
-      cd.clear();
-      for (size_t g = 0; g < who.size(); g++) {
-        BatchSlot &s = slots[who[g]];
-        cd.push_back(mib::CopyDesc{s.d->d_buf + s.d->deliv, s.d_dst, len[g]});
-        s.d_dst += len[g];
-        s.room -= len[g];
-        s.given += len[g];
-      }
-      if ((rc = copy_batch(c, cd)) != 0) return rc;
-      HIP_OK(hipStreamSynchronize(c->stream));
-      t4 = t5 = clk::now();
-    } else if (!who.empty()) {
-      // every session's bytes to the staging span, the span down in one copy
-      gd.clear();
-      dst.resize(who.size());
-      const uint64_t total = mib::plan_gather(len.data(), len.size(), dst.data());
-      for (size_t g = 0; g < who.size(); g++)
-        gd.push_back(mib::GatherDesc{slots[who[g]].d->d_buf + slots[who[g]].d->deliv, len[g], dst[g]});
-      c->sspan_trim.need = std::max(c->sspan_trim.need, total);
-      if ((rc = grow((void **)&c->d_sspan, &c->sspan_bytes, total)) != 0) return rc;
-      // (the descriptors take the place of the jobs, which are read)
-      if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, gd.size() * sizeof(mib::GatherDesc))) != 0) return rc;
-      HIP_OK(hipMemcpyAsync(c->d_sbatch, gd.data(), gd.size() * sizeof(mib::GatherDesc), hipMemcpyHostToDevice, c->stream));
-      for (size_t g0 = 0; g0 < gd.size(); g0 += mib::kGatherMaxDescs) {
-        const size_t g1 = std::min(gd.size(), g0 + mib::kGatherMaxDescs);
-        HIP_OK(mib_stream_gather_launch((const mib::GatherDesc *)c->d_sbatch + g0, (uint32_t)(g1 - g0),
-                                        mib::gather_blocks(len.data() + g0, g1 - g0), c->d_sspan, c->stream));
-      }
-      t4 = clk::now();
-      span.resize(total);
-      const mib::HostPiece down{span.data(), c->d_sspan, total};
-      if ((rc = mib::ctx_download(c, c->stream, &down, 1)) != 0) return rc;
-      for (size_t g = 0; g < who.size(); g++) {
-        std::vector<uint8_t> &got = slots[who[g]].got;
-        got.insert(got.end(), span.begin() + dst[g], span.begin() + dst[g] + len[g]);
-      }
-      t5 = clk::now();
-    }
-    for (size_t g = 0; g < who.size(); g++) slots[who[g]].d->deliv += len[g];
-    g_batch_ms[0] += ms_between(t[0], t[1]);
-    g_batch_ms[1] += ms_between(t[1], t[2]);
-    g_batch_ms[2] += ms_between(t[2], t[3]);
-    g_batch_ms[3] += ms_between(t[3], t4);
-    g_batch_ms[4] += ms_between(t4, t5);
-    // who goes on: a launch to make or bytes held, and room for them
-    next.clear();
-    for (size_t i : act) {
-      const BatchSlot &s = slots[i];
-      if (!s.rc && (s.run || held(s.d)) && s.room > 0) next.push_back(i);
-    }
-    act.swap(next);
-  }
-  // a slot whose range ran out before its launch could be made owes it to the next call
-  for (BatchSlot &s : slots)
-    if (!s.d->error) s.d->due = s.run && !s.rc;
-  // input no resume reads again leaves the front of the pending bytes (once it is worth a move):
-  // every session's move in one launch
-  moves.clear();
-  for (BatchSlot &s : slots) {
-    if (!s.suspended || s.rc) continue;
-    mib_decoder *d = s.d;
-    const uint64_t keep = mib::stream_keep_from(d->ck);
-    if (keep >= (64u << 10) && 2 * keep >= d->in_len) {
-      moves.push_back(mib::MoveDesc{d->d_in, keep, d->in_len - keep});
-      d->in_len -= keep;
-      d->need_len = d->need_len > keep ? d->need_len - keep : 0;
-      mib::stream_rebase_input(&d->ck, keep);   // (the session's next launch brings the rebased head)
-      s.run = true;   // until the move is done: a device failure in it ends this session too
-    }
-  }
-  if (!moves.empty()) {
-    host.clear();
-    const uint64_t units_at = stage_moves(moves, units, 0, host);
-    if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, host.size())) != 0) return rc;
-    HIP_OK(hipMemcpyAsync(c->d_sbatch, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(mib_stream_move_batch_launch((const mib::MoveDesc *)c->d_sbatch, (const mib::MoveUnit *)(c->d_sbatch + units_at),
-                                        (uint32_t)units.size(), c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    for (BatchSlot &s : slots) s.run = false;
-  }
-  return 0;
-}
-
 // Where a call's chunks come from and where its bytes go: host memory (in, out) or, for the
 // device-resident calls, ranges of two device buffers given by host offset arrays.
 struct BatchIo {
@@ -1699,6 +1423,130 @@ struct BatchIo {
   uint64_t *out_sizes = nullptr;
   size_t chunk(size_t i, bool finish) const {
     return finish ? 0 : device ? (size_t)(in_offsets[i + 1] - in_offsets[i]) : in[i].size;
+  }
+};
+
+// The device's part of a call's rounds (mib::stream_rounds decides, this does): slot i is
+// session d[i].  It also takes the timestamps of the five legs (mib_decoder_batch_times).
+struct RoundsDev {
+  using clk = std::chrono::steady_clock;
+  mib_ctx *c;
+  mib_decoder *const *d;
+  const BatchIo &io;
+  std::vector<uint8_t> host, span;
+  std::vector<mib::MoveDesc> moves;
+  std::vector<mib::MoveUnit> units;
+  std::vector<mib::CopyDesc> cd;
+  std::vector<uint64_t> dst;
+  clk::time_point t3 = clk::now();   // where the delivery leg starts: the end of the read-back, or of the last round
+
+  // the moves' descriptors at host[at] and their blocks (plan_moves) behind them; `host` goes up
+  // to the front of the context's batch buffer and the moves run
+  int run_moves(uint64_t at) {
+    mib::plan_moves(moves.data(), moves.size(), units);
+    const uint64_t units_at = (at + moves.size() * sizeof(mib::MoveDesc) + 15) & ~15ull;
+    host.resize(units_at + units.size() * sizeof(mib::MoveUnit));
+    if (!moves.empty()) memcpy(host.data() + at, moves.data(), moves.size() * sizeof(mib::MoveDesc));
+    if (!units.empty()) memcpy(host.data() + units_at, units.data(), units.size() * sizeof(mib::MoveUnit));
+    int rc;
+    if ((rc = grow((void **)&c->d_sbatch, &c->sbatch_bytes, host.size())) != 0) return rc;
+    HIP_OK(hipMemcpyAsync(c->d_sbatch, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+    return mib_stream_move_batch_launch((const mib::MoveDesc *)(c->d_sbatch + at), (const mib::MoveUnit *)(c->d_sbatch + units_at),
+                                        (uint32_t)units.size(), c->stream) == hipSuccess ? 0 : MIB_E_NO_DEVICE;
+  }
+
+  // One round's decode launch over the slots `jobs`, each of which holds nothing: the histories
+  // move, the jobs go up, ONE launch runs them, jobs and checkpoint heads come back.
+  int launch(const std::vector<size_t> &jobs, const std::vector<mib::StreamPlan> &plans, int final, mib::StreamJob *ret,
+             uint8_t *heads) {
+    const auto t0 = clk::now();
+    const int cus = (c->device >= 0 && c->device < kMaxDevices && g_dev_cus[c->device] > 0) ? g_dev_cus[c->device] : 256;
+    int rc;
+    const size_t k = jobs.size();
+    // [jobs][heads][move descriptors][move units]: one upload; the first two come back
+    const uint64_t heads_at = mib::stream_heads_offset(k, sizeof(mib::StreamJob));
+    const uint64_t moves_at = (heads_at + k * kCkHead + 15) & ~15ull;
+    host.assign(moves_at, 0);
+    moves.clear();
+    for (size_t a = 0; a < k; a++) {
+      const mib_decoder *s = d[jobs[a]];
+      // the history to the buffer's front: the launch needs out_window + slack behind pos
+      if (plans[a].move) moves.push_back(mib::MoveDesc{s->d_buf, plans[a].move, s->ck.e.pos});
+      // (in, in_len, buf, buf_cap, out_limit, dict, dict_len, ck, lgwin, final; the kernel's fields 0)
+      const mib::StreamJob j{s->d_in, s->in_len, s->d_buf, s->buf_cap, plans[a].out_limit, s->d_dict,
+                             s->has_dict ? s->dict.size() : 0, s->d_ck, s->lgwin, final, 0, 0, 0, 0, 0};
+      memcpy(host.data() + a * sizeof(j), &j, sizeof(j));
+      memcpy(host.data() + heads_at + a * kCkHead, &s->ck, kCkHead);
+    }
+    const int per_cu = __atomic_load_n(&g_force_small_decoder, __ATOMIC_RELAXED) ? 4 : waves_per_cu(c->device, k);
+    const int grid = mib::stream_batch_grid(k, cus, per_cu, __atomic_load_n(&g_decoder_grid_cap, __ATOMIC_RELAXED));
+    c->scratch_trim.need = std::max(c->scratch_trim.need, kStreamScratch * (uint64_t)grid);
+    if ((rc = grow((void **)&c->d_scratch, &c->scratch_bytes, kStreamScratch * (uint64_t)grid)) != 0) return rc;
+    if ((rc = run_moves(moves_at)) != 0) return rc;
+    const auto t1 = clk::now();
+    HIP_OK(mib_decode_resume_launch((mib::StreamJob *)c->d_sbatch, (int)k, c->d_scratch, kStreamScratch, grid, per_cu,
+                                    c->d_sbatch + heads_at, c->stream));
+    __atomic_add_fetch(&g_batch_launches, 1, __ATOMIC_RELAXED);
+    // (waiting here, not in the copy, costs nothing -- the copy into pageable memory waits for the
+    // launch anyway -- and lets mib_decoder_batch_times tell the launch from the read-back)
+    HIP_OK(hipStreamSynchronize(c->stream));
+    const auto t2 = clk::now();
+    HIP_OK(hipMemcpyAsync(host.data(), c->d_sbatch, heads_at + k * kCkHead, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    memcpy(ret, host.data(), k * sizeof(mib::StreamJob));
+    memcpy(heads, host.data() + heads_at, k * kCkHead);
+    t3 = clk::now();
+    g_batch_ms[0] += ms_between(t0, t1);
+    g_batch_ms[1] += ms_between(t1, t2);
+    g_batch_ms[2] += ms_between(t2, t3);
+    return 0;
+  }
+
+  // One copy launch for every slot's bytes: into the callers' ranges (nothing comes down), or
+  // into the staging span (plan_gather), which comes down in one copy and is cut into `got`.
+  int deliver(std::vector<mib::StreamSlot> &slots, const std::vector<size_t> &who, const std::vector<uint64_t> &len) {
+    if (who.empty()) return 0;
+    int rc;
+    uint64_t total = 0;
+    if (!io.device) {
+      dst.resize(who.size());
+      total = mib::plan_gather(len.data(), len.size(), dst.data());
+      c->sspan_trim.need = std::max(c->sspan_trim.need, total);
+      if ((rc = grow((void **)&c->d_sspan, &c->sspan_bytes, total)) != 0) return rc;
+    }
+    cd.clear();
+    for (size_t g = 0; g < who.size(); g++) {
+      const size_t i = who[g];
+      cd.push_back(mib::CopyDesc{d[i]->d_buf + d[i]->deliv,
+                                 io.device ? io.d_out + io.out_offsets[i] + slots[i].given : c->d_sspan + dst[g], len[g]});
+    }
+    if ((rc = copy_batch(c, cd)) != 0) return rc;   // (the descriptors take the place of the jobs, which are read)
+    if (io.device) HIP_OK(hipStreamSynchronize(c->stream));   // (a host call waits in its download)
+    const auto t4 = clk::now();
+    if (!io.device) {
+      span.resize(total);
+      const mib::HostPiece down{span.data(), c->d_sspan, total};
+      if ((rc = mib::ctx_download(c, c->stream, &down, 1)) != 0) return rc;
+      for (size_t g = 0; g < who.size(); g++) {
+        std::vector<uint8_t> &got = slots[who[g]].got;
+        got.insert(got.end(), span.begin() + dst[g], span.begin() + dst[g] + len[g]);
+      }
+      g_batch_ms[4] += ms_between(t4, clk::now());
+    }
+    g_batch_ms[3] += ms_between(t3, t4);
+    t3 = clk::now();
+    return 0;
+  }
+
+  // every session's input move in one launch: in[0, in_len) <- in[drop, drop + in_len)
+  int move_inputs(const std::vector<size_t> &who, const std::vector<uint64_t> &drop) {
+    int rc;
+    moves.clear();
+    for (size_t g = 0; g < who.size(); g++) moves.push_back(mib::MoveDesc{d[who[g]]->d_in, drop[g], d[who[g]]->in_len});
+    host.clear();
+    if ((rc = run_moves(0)) != 0) return rc;
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
   }
 };
 
@@ -1721,81 +1569,65 @@ int fetch_first_bytes(mib_ctx *c, const BatchIo &io, const std::vector<size_t> &
 
 // update or finish of k sessions, already checked (decoder_batch_check)
 int decoder_batch(mib_decoder *const *d, const BatchIo &io, size_t k, int *status, bool finish) {
-  // a call whose sessions all return without a launch or a delivery (failed, finished, nothing to
-  // add, nothing held) needs no device
+  // what each session does in this call; a call whose sessions all return without a launch or a
+  // delivery (failed, finished, nothing to add, nothing held) needs no device
+  std::vector<mib::StreamAdmit> admit(k);
+  std::vector<size_t> open;   // the slots whose session opens on a chunk in device memory
   bool device = false;
-  for (size_t i = 0; i < k; i++)
-    if (!d[i]->error && (held(d[i]) || d[i]->due || (!d[i]->finished && (finish || io.chunk(i, finish))))) device = true;
-  struct Hold {   // (the default context for the whole call, taken only when a session needs the device)
-    bool on = false;
-    ~Hold() { if (on) mib_default_lock(0); }
-  } hold;
+  for (size_t i = 0; i < k; i++) {
+    admit[i] = mib::stream_admit(*d[i], io.chunk(i, finish), finish);
+    if (mib::stream_admit_needs_device(admit[i], *d[i])) device = true;
+    if (io.device && !finish && admit[i] == mib::StreamAdmit::kFeed && !d[i]->lgwin) open.push_back(i);
+  }
+  std::unique_ptr<DefaultUse> hold;   // (the default context for the whole call, taken only when a session needs the device)
   mib_ctx *c = nullptr;
   if (device) {
-    mib_default_lock(1);
-    hold.on = true;
+    hold.reset(new DefaultUse);
     c = default_ctx();
     if (!c) return MIB_E_NO_DEVICE;
     hipSetDevice(c->device);
   }
-  std::vector<BatchSlot> slots(k);
+  std::vector<mib::StreamSlot> slots(k);
   std::vector<mib::HostPiece> up;
   std::vector<mib::CopyDesc> app;
-  std::vector<size_t> open;
   std::vector<uint8_t> first;
-  int rc = 0;
-  if (io.device && !finish) {
-    for (size_t i = 0; i < k; i++)
-      if (!d[i]->error && !d[i]->finished && !d[i]->lgwin && io.chunk(i, finish)) open.push_back(i);
-    if (!open.empty()) rc = fetch_first_bytes(c, io, open, first);
-  }
+  int rc = fetch_first_bytes(c, io, open, first);
   size_t opened = 0;
   for (size_t i = 0; i < k; i++) {
-    BatchSlot &s = slots[i];
-    s.d = d[i];
+    mib::StreamSlot &s = slots[i];
+    s.s = d[i];
     status[i] = 0;
     if (io.device) {
       io.out_sizes[i] = 0;
-      s.d_dst = io.d_out + io.out_offsets[i];
       s.room = io.out_offsets[i + 1] - io.out_offsets[i];
-    } else {
-      io.out[i].data = nullptr;
-      io.out[i].size = 0;
-    }
-    if (d[i]->error) continue;
+    } else io.out[i] = mib_buf{nullptr, 0};
+    mib::stream_admit_slot(s, admit[i]);
+    if (admit[i] != mib::StreamAdmit::kNothing && !d[i]->finished) d[i]->device = c->device;
+    if (admit[i] != mib::StreamAdmit::kFeed) continue;
     const size_t n = io.chunk(i, finish);
-    // bytes held or a launch owed (a device-resident call ran out of room): this call goes on there
-    const bool pending = held(d[i]) || d[i]->due;
-    if (!pending && (finish ? d[i]->finished : n == 0)) continue;   // returns 0 and nothing
-    if (d[i]->finished) {
-      if (n) s.rc = -17;
-      continue;   // (what it holds is delivered)
+    if (rc) { s.rc = rc; continue; }   // the first bytes did not come: the call fails below
+    // no byte at all (finish): the decoder reads an empty input's padding, window bits 0 (16) first
+    if (!d[i]->lgwin) s.rc = decoder_open(d[i], c, finish ? 0 : io.device ? first[opened++] : io.in[i].data[0]);
+    if (!s.rc) s.rc = decoder_reserve(d[i], c, n);
+    if (s.rc) continue;
+    if (n) {
+      if (io.device) app.push_back(mib::CopyDesc{io.d_in + io.in_offsets[i], d[i]->d_in + d[i]->in_len, n});
+      else up.push_back(mib::HostPiece{d[i]->d_in + d[i]->in_len, io.in[i].data, n});
     }
-    d[i]->device = c->device;
-    if (finish || n) {
-      if (rc) { s.rc = rc; continue; }   // the first bytes did not come: the call fails below
-      // no byte at all (finish): the decoder reads an empty input's padding, window bits 0 (16) first
-      if (!d[i]->lgwin) s.rc = decoder_open(d[i], c, finish ? 0 : io.device ? first[opened++] : io.in[i].data[0]);
-      if (!s.rc) s.rc = decoder_reserve(d[i], c, n);
-      if (s.rc) continue;
-      if (n) {
-        if (io.device) app.push_back(mib::CopyDesc{io.d_in + io.in_offsets[i], d[i]->d_in + d[i]->in_len, n});
-        else up.push_back(mib::HostPiece{d[i]->d_in + d[i]->in_len, io.in[i].data, n});
-        d[i]->in_len += n;
-      }
-      s.run = true;
-    } else {
-      s.run = d[i]->due;
-    }
+    d[i]->in_len += n;
+    s.run = true;
   }
   // every slot's chunk behind its session's pending input: one copy launch, or the host's pieces
   if (!rc && !app.empty()) rc = copy_batch(c, app);
   if (!rc && !up.empty()) rc = mib::ctx_upload(c, c->stream, up.data(), up.size());
-  if (!rc && c) rc = decoder_batch_rounds(c, slots, finish ? 1 : 0, io.device);
+  if (!rc && c) {
+    RoundsDev dev{c, d, io};
+    rc = mib::stream_rounds(dev, slots, finish ? 1 : 0);
+  }
   for (size_t i = 0; i < k; i++) {
-    BatchSlot &s = slots[i];
+    mib::StreamSlot &s = slots[i];
     if (d[i]->error) { status[i] = d[i]->error; continue; }
-    if (rc && (s.run || held(d[i]))) s.rc = rc;   // a device failure ends the sessions that still had work
+    if (rc && (s.run || mib::held(*d[i]))) s.rc = rc;   // a device failure ends the sessions that still had work
     if (!io.device) {
       status[i] = decoder_result(d[i], s.rc, s.got, &io.out[i]);
     } else if (s.rc) {
@@ -1804,7 +1636,7 @@ int decoder_batch(mib_decoder *const *d, const BatchIo &io, size_t k, int *statu
       io.out_sizes[i] = none.size;   // (MIB_E_OUTPUT_LIMIT: the total, as in the host call)
     } else {
       io.out_sizes[i] = s.given;
-      status[i] = mib::stream_more_output(held(d[i]), s.room, d[i]->due) ? MIB_DEC_MORE_OUTPUT : 0;
+      status[i] = mib::stream_more_output(mib::held(*d[i]), s.room, d[i]->due) ? MIB_DEC_MORE_OUTPUT : 0;
     }
   }
   return 0;
@@ -1825,10 +1657,7 @@ int decoder_batch_host(mib_decoder *const *d, const mib_span *in, size_t k, mib_
   if (!out || !status || (!finish && !in) || decoder_batch_check(d, k)) return MIB_E_INVALID_ARG;
   for (size_t i = 0; i < k; i++)
     if (!finish && !in[i].data && in[i].size) return MIB_E_INVALID_ARG;
-  BatchIo io;
-  io.in = in;
-  io.out = out;
-  return decoder_batch(d, io, k, status, finish);
+  return decoder_batch(d, BatchIo{in, out}, k, status, finish);
 }
 
 int decoder_batch_device(mib_decoder *const *d, const uint8_t *d_in, const uint64_t *in_offsets, size_t k, uint8_t *d_out,
@@ -1838,14 +1667,7 @@ int decoder_batch_device(mib_decoder *const *d, const uint8_t *d_in, const uint6
   for (size_t i = 0; i < k; i++)
     if (out_offsets[i + 1] < out_offsets[i] || (!finish && in_offsets[i + 1] < in_offsets[i])) return MIB_E_INVALID_ARG;
   if ((!d_out && out_offsets[k] > out_offsets[0]) || (!finish && !d_in && in_offsets[k] > in_offsets[0])) return MIB_E_INVALID_ARG;
-  BatchIo io;
-  io.device = true;
-  io.d_in = d_in;
-  io.in_offsets = in_offsets;
-  io.d_out = d_out;
-  io.out_offsets = out_offsets;
-  io.out_sizes = out_sizes;
-  return decoder_batch(d, io, k, status, finish);
+  return decoder_batch(d, BatchIo{nullptr, nullptr, true, d_in, in_offsets, d_out, out_offsets, out_sizes}, k, status, finish);
 }
 }  // namespace
 

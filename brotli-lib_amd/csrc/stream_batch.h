@@ -1,9 +1,9 @@
 // The rounds of the streaming decoder's calls, one session's or many (mib_decoder_update,
 // mib_decoder_update_batch; DESIGN.md §4d "Rounds"): the descriptors the host and the move and
-// gather kernels of decode_stream.hip share, and the planning of a round -- which sessions
+// copy kernels of decode_stream.hip share, and the planning of a round -- which sessions
 // launch, where each session's output lies in the staging span, which block moves which tiles,
-// how large the decode grid is, and for the device-resident calls how much a slot delivers,
-// what it goes on holding and when it launches.  Plain C++ (no HIP types):
+// how large the decode grid is, how much a slot delivers, what it goes on holding and when it
+// launches (stream_rounds.h holds the loop over them).  Plain C++ (no HIP types):
 // the planning is exercised by a stand-alone host program under sanitizers
 // (tests/stream_batch_host_main.cpp).
 #pragma once
@@ -24,10 +24,13 @@ struct MoveDesc {
 struct MoveUnit {
   uint32_t desc, tile0, step, reserved;
 };
-// span[dst, dst + n) <- src[0, n): a session's new output goes to the staging span
-struct GatherDesc {
+// dst[0, n) <- src[0, n), both of any alignment and pointers of their own: a slot's chunk goes
+// to its session's pending input, a session's decoded bytes go to the caller's range or to the
+// staging span
+struct CopyDesc {
   const uint8_t *src;
-  uint64_t n, dst;
+  uint8_t *dst;
+  uint64_t n;
 };
 
 constexpr int kMoveThreads = 1024;
@@ -59,8 +62,8 @@ inline void plan_moves(const MoveDesc *d, size_t k, std::vector<MoveUnit> &units
 }
 
 // Where each session's [start, out_pos) goes in the staging span: dense, in session order,
-// each range starting on a 16-byte boundary (the gather kernel stores whole 16-byte vectors).
-// Returns the span's size.
+// each range starting on a 16-byte boundary (so the copy kernel stores whole 16-byte vectors up
+// to a range's last granule).  Returns the span's size.
 inline uint64_t plan_gather(const uint64_t *len, size_t k, uint64_t *dst) {
   uint64_t at = 0;
   for (size_t i = 0; i < k; i++) {
@@ -68,15 +71,6 @@ inline uint64_t plan_gather(const uint64_t *len, size_t k, uint64_t *dst) {
     at += (len[i] + 15) & ~15ull;
   }
   return at;
-}
-// blocks per descriptor (the grid's x extent) of a gather launch over these lengths
-inline uint32_t gather_blocks(const uint64_t *len, size_t k) {
-  uint64_t most = 1;
-  for (size_t i = 0; i < k; i++) {
-    const uint64_t t = tiles_of(0, len[i], kGatherTile);
-    if (t > most) most = t;
-  }
-  return (uint32_t)(most < kGatherSpread ? most : kGatherSpread);
 }
 
 // A session launches in the first round of a call unless its last launch stopped in front of a
@@ -98,15 +92,8 @@ inline int stream_batch_grid(size_t jobs, int cus, int per_cu, int cap) {
   return (int)g;
 }
 
-// ---------------------------------------------------------------- device-resident batches
-// (mib_decoder_update_batch_device, DESIGN.md §4d "Device-resident batches")
-// dst[0, n) <- src[0, n), both of any alignment and pointers of their own: a slot's chunk goes
-// to its session's pending input, a session's decoded bytes go to the caller's range
-struct CopyDesc {
-  const uint8_t *src;
-  uint8_t *dst;
-  uint64_t n;
-};
+// ---------------------------------------------------------------- delivery
+// (DESIGN.md §4d "Device-resident batches")
 constexpr uint64_t kNoRoomLimit = ~0ull;   // a host call's slot: its results grow as needed
 
 // A session between launches may hold decoded bytes the caller has not fetched, held = pos -

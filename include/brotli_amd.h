@@ -192,9 +192,10 @@ int mib_debug_copy_batch(const uint8_t *const *d_src, uint8_t *const *d_dst, con
 void mib_decoder_batch_stats(uint64_t *launches);
 /* Diagnostic (scripts/stream_decode_rate.py): host wall time the rounds of the decode launches
  * made by the session entry points have spent since process start, ms[0..4] = upload (jobs,
- * heads, move descriptors; the move launch), the decode launch until it is done, the read-back of jobs and heads, the gather (descriptors and
- * launch; a device-resident call: its delivery launch), the download of the span and its cutting
- * into results (a device-resident call adds nothing here). */
+ * heads, move descriptors; the move launch), the decode launch until it is done, the read-back of
+ * jobs and heads, the delivery (copy descriptors and copy launch: into the staging span, or for a
+ * device-resident call into the callers' ranges), the download of the span and its cutting into
+ * results (a device-resident call adds nothing here). */
 void mib_decoder_batch_times(double *ms, int n);
 /* Diagnostic (tests): at most this many blocks per batch launch (0: the default), so a small
  * batch runs the kernel's job loop more than once per block. */

@@ -161,7 +161,7 @@ def sessions(a):
         best_s = ts if best_s is None or ts < best_s else best_s
     dt, _, launches, ms, rounds = best_b
     solo_rate = sum(len(p) for p in plains[:m]) / best_s / 1e6
-    names = ('upload_ms', 'launch_ms', 'readback_ms', 'gather_ms', 'download_ms')
+    names = ('upload_ms', 'launch_ms', 'readback_ms', 'delivery_ms', 'download_ms')
     res = {'sessions': k, 'quality': a.quality, 'update_bytes': chunk, 'out_window': a.out_window or (16 << 20),
            'updates_per_session': steps, 'batch_MBps': round(total / dt / 1e6, 1),
            'solo_sessions_timed': m, 'one_after_another_MBps': round(solo_rate, 2),

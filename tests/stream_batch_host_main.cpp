@@ -1,7 +1,7 @@
 // The planning of a batch of streaming decoder sessions (brotli-lib_amd/csrc/stream_batch.h)
 // driven with seeded random session states, stand-alone so that it runs under AddressSanitizer
 // and UBSan (tests/test_stream_batch_host.py).  The kernels' walks are replayed on the host:
-// which bytes each (block, tile, thread) of a move or gather launch touches is plain arithmetic.
+// which bytes each (block, tile, thread) of a move or copy launch touches is plain arithmetic.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -31,6 +31,8 @@ static uint64_t below(uint64_t n) { return n ? rnd() % n : 0; }
       exit(1);                                                         \
     }                                                                  \
   } while (0)
+
+#include "stream_copy_walk.h"
 
 // one tile of copy_tile (decode_stream.hip): the destination offsets thread `tid` stores
 static void tile_bytes(uint64_t mis, uint64_t n, uint64_t tile, int threads, int tid, int64_t *lo, int64_t *hi) {
@@ -113,13 +115,23 @@ static void test_moves(int rounds) {
   printf("moves: %d batches ok\n", rounds);
 }
 
+// A host call's delivery: plan_gather lays the sessions' ranges out in the staging span, one
+// CopyDesc per range goes through plan_copies, and the copy kernel's walk is replayed.  Every
+// span byte of every range is written exactly once with its source byte, nothing is written
+// outside the ranges, and ranges start on 16-byte boundaries.  Sources have any alignment, as a
+// session's `deliv` has in its buffer.
 static void test_gather(int rounds) {
   for (int r = 0; r < rounds; r++) {
     const size_t k = 1 + below(40);
-    std::vector<uint64_t> len(k), dst(k);
-    for (size_t i = 0; i < k; i++) len[i] = below(3) == 0 ? 0 : below(4) == 0 ? below(50) : below(6 * kGatherTile);
+    std::vector<uint64_t> len(k), dst(k), sat(k);
+    uint64_t stotal = 0;
+    for (size_t i = 0; i < k; i++) {
+      len[i] = below(3) == 0 ? 0 : below(4) == 0 ? below(50) : below(6 * kGatherTile);
+      if (r % 20 == 3 && i == 0) len[i] = (kGatherSpread + 1) * kGatherTile + 1;   // more tiles than blocks
+      sat[i] = stotal + below(16);
+      stotal = sat[i] + len[i];
+    }
     const uint64_t total = plan_gather(len.data(), k, dst.data());
-    std::vector<uint8_t> span(total, 0), cover(total, 0);
     uint64_t prev_end = 0;
     for (size_t i = 0; i < k; i++) {
       CHECK(dst[i] % 16 == 0);
@@ -128,24 +140,34 @@ static void test_gather(int rounds) {
       prev_end = dst[i] + len[i];
     }
     CHECK(total % 16 == 0 && total < prev_end + 16);
-    const uint32_t blocks = gather_blocks(len.data(), k);
-    CHECK(blocks >= 1 && blocks <= kGatherSpread);
-    for (size_t i = 0; i < k; i++) {
-      std::vector<uint8_t> src(len[i]);
-      for (auto &b : src) b = (uint8_t)rnd();
-      const uint64_t tiles = tiles_of(0, len[i], kGatherTile);
-      for (uint32_t b = 0; b < blocks; b++)
-        for (uint64_t t = b; t < tiles; t += blocks)
-          for (int tid = 0; tid < kGatherThreads; tid++) {
-            int64_t lo, hi;
-            tile_bytes(0, len[i], t, kGatherThreads, tid, &lo, &hi);
-            for (int64_t x = lo; x < hi; x++) {
-              span[dst[i] + (uint64_t)x] = src[(size_t)x];
-              cover[dst[i] + (uint64_t)x]++;
-            }
-          }
-      for (uint64_t x = 0; x < len[i]; x++) CHECK(cover[dst[i] + x] == 1 && span[dst[i] + x] == src[x]);
+    // a 16-byte aligned span, as the device allocation is, with room to see a store outside it
+    std::vector<uint8_t> mem(total + 48, 0xC5), cover(total + 48, 0), smem(stotal + 32);
+    uint8_t *span = mem.data() + 16 + ((16 - ((uintptr_t)mem.data() & 15)) & 15);
+    for (auto &b : smem) b = (uint8_t)rnd();
+    std::vector<CopyDesc> d(k);
+    for (size_t i = 0; i < k; i++) d[i] = CopyDesc{smem.data() + sat[i], span + dst[i], len[i]};
+    std::vector<CopyLaunch> ls;
+    plan_copies(d.data(), k, r % 3 == 0 ? 1 + below(5) : kGatherMaxDescs, ls);
+    size_t next = 0;
+    for (const CopyLaunch &l : ls) {
+      CHECK(l.first == next && l.count >= 1);
+      CHECK(l.blocks >= 1 && l.blocks <= kGatherSpread);
+      // the grid is the one the lengths alone give: ranges start on granules
+      uint64_t most = 1;
+      for (size_t y = 0; y < l.count; y++) most = std::max(most, tiles_of(0, len[l.first + y], kGatherTile));
+      CHECK(l.blocks == std::min<uint64_t>(most, kGatherSpread));
+      next += l.count;
     }
+    CHECK(next == k);
+    replay_copies(d.data(), ls, mem.data(), cover);
+    std::vector<uint8_t> want(mem.size(), 0xC5), wcover(mem.size(), 0);
+    for (size_t i = 0; i < k; i++)
+      for (uint64_t x = 0; x < len[i]; x++) {
+        want[(size_t)(span + dst[i] + x - mem.data())] = smem[sat[i] + x];
+        wcover[(size_t)(span + dst[i] + x - mem.data())] = 1;
+      }
+    CHECK(mem == want);
+    CHECK(cover == wcover);
   }
   printf("gather: %d batches ok\n", rounds);
 }
@@ -189,8 +211,8 @@ static void test_rounds(int rounds) {
 }
 
 int main() {
-  static_assert(sizeof(MoveDesc) == 24 && sizeof(MoveUnit) == 16 && sizeof(GatherDesc) == 24, "descriptor layouts");
-  static_assert(sizeof(GatherDesc) <= sizeof(StreamJob), "gather descriptors reuse the jobs' place");
+  static_assert(sizeof(MoveDesc) == 24 && sizeof(MoveUnit) == 16 && sizeof(CopyDesc) == 24, "descriptor layouts");
+  static_assert(sizeof(CopyDesc) <= sizeof(StreamJob), "copy descriptors reuse the jobs' place");
   test_moves(60);
   test_gather(60);
   test_rounds(20000);

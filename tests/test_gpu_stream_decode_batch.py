@@ -420,3 +420,44 @@ def test_interleaving_and_other_entry_points():
     assert b''.join(got_b) == other_full and b.finished
     assert brotli_amd.decoder_finish_batch([a, b]) == [b'', b'']
     assert brotli_amd.brotliDecode(enc) == plain
+
+
+# kGatherTile = 4096 bytes; 1 MiB + 1 is the first length whose tiles exceed kGatherSpread = 256
+# blocks, so a block of the copy launch walks more than one tile
+DELIVERY_SIZES = (1, 15, 16, 17, 4095, 4096, 4097, (1 << 20) + 1)
+DELIVERY_HEAD = 5   # the first metablock's bytes: odd, so what follows starts off a 16-byte granule
+
+
+def test_host_delivery_through_the_copy_kernel():
+    """host delivery at the sizes where the copy launch can go wrong: one call whose sessions'
+    single launch decodes 1 ... 1 MiB + 1 bytes (under, at and over a 16-byte granule and a tile;
+    more tiles than blocks), then the same streams in two chunks each, cut inside their second
+    uncompressed metablock, so that the second call's bytes start at `deliv` = 5 in the session
+    buffer.  Every byte against the plaintext."""
+    assert ((1 << 20) + 4095) // 4096 == 256 and ((1 << 20) + 1 + 4095) // 4096 > 256
+    rng = random.Random(12)
+    plains, datas = [], []
+    for n in DELIVERY_SIZES:
+        plain = rng.randbytes(n)
+        parts = [plain[:DELIVERY_HEAD], plain[DELIVERY_HEAD:]]
+        st = S.Stream(22, [S.MB('raw', data=p) for p in parts if p] + [S.MB('empty')])
+        assert S.model(st) == plain
+        plains.append(plain)
+        datas.append(S.build(st).data)
+    ds = [brotli_amd.BrotliDecoder() for _ in datas]
+    before = _batch_launches()
+    out = brotli_amd.decoder_update_batch(ds, datas)
+    assert _batch_launches() - before == 1 and all(d.passes == 1 for d in ds)
+    assert [len(o) for o in out] == list(DELIVERY_SIZES)
+    assert out == plains
+    assert all(d.finished for d in ds) and brotli_amd.decoder_finish_batch(ds) == [b''] * len(ds)
+    # two chunks: the cut leaves the last byte of the second metablock (and the stream's end) out
+    cuts = [len(data) - 1 - (max(len(plain) - DELIVERY_HEAD, 0) + 1) // 2 for data, plain in zip(datas, plains)]
+    ds = [brotli_amd.BrotliDecoder() for _ in datas]
+    first = brotli_amd.decoder_update_batch(ds, [data[:c] for data, c in zip(datas, cuts)])
+    second = brotli_amd.decoder_update_batch(ds, [data[c:] for data, c in zip(datas, cuts)])
+    for n, plain, a, b in zip(DELIVERY_SIZES, plains, first, second):
+        if n > DELIVERY_HEAD:   # an uncompressed metablock comes whole or not at all
+            assert a == plain[:DELIVERY_HEAD], n
+        assert a + b == plain, n
+    assert all(d.finished for d in ds) and brotli_amd.decoder_finish_batch(ds) == [b''] * len(ds)

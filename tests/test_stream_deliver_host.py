@@ -1,8 +1,9 @@
-"""The planning of the device-resident session calls (brotli-lib_amd/csrc/stream_batch.h: what a
-slot delivers and goes on holding, when it launches and with which output limit, when it reports
-MORE_OUTPUT, the copy launches' grids and their split) in a stand-alone program under
-AddressSanitizer and UBSan (tests/stream_deliver_host_main.cpp).  No GPU, nothing loaded into
-Python."""
+"""The rounds of the session calls -- mib::stream_rounds, the product's own loop
+(brotli-lib_amd/csrc/stream_rounds.h: admission, who launches and with which output limit, the
+accounting of a launch, what a slot delivers and goes on holding, when it reports MORE_OUTPUT,
+input compaction) over a model device, and the copy launches' grids and their split
+(stream_batch.h) -- in a stand-alone program under AddressSanitizer and UBSan
+(tests/stream_deliver_host_main.cpp).  No GPU, nothing loaded into Python."""
 import os
 import shutil
 import subprocess
@@ -23,4 +24,4 @@ def test_delivery_planning_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     assert 'Sanitizer' not in r.stderr and 'runtime error' not in r.stderr, r.stderr[-4000:]
-    assert r.stdout.count(' ok') == 3, r.stdout
+    assert r.stdout.count(' ok') == 7, r.stdout
