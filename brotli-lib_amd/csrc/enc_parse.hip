@@ -114,18 +114,16 @@ __device__ __forceinline__ uint32_t ins_extra_sel(int ic) {
 
 struct Staged {   // one position's parse inputs as loaded
   uint32_t m[kMaxMatches];
-  uint32_t nm;
   uint32_t lit;
   uint32_t w0, w1;   // (KC) the position's first 8 bytes: words[g], words[g + 4]
 };
 template <bool KC>
 __device__ __forceinline__ void load_staged(Staged &st, const uint32_t *matches, const uint8_t *data, const uint32_t *words,
                                             uint32_t g, uint32_t p) {
-  st.lit = data[p];
-  rec_load(matches + (uint64_t)g * kMatchRec, st.m);   // 0 = no entry
-  st.nm = 0;
-#pragma unroll
-  for (int q = 0; q < kMaxMatches; q++) st.nm += st.m[q] != 0u;
+  st.lit = ((GCU8 *)data)[p];   // (a global load: a flat one, pending a batch long, shares the LDS reads' counter)
+  // (0 = no entry.  Nothing here uses what it loads: the next batch's record stays in flight
+  // until stage() takes it, a batch later; counting its entries here waited for it at once.)
+  rec_load(matches + (uint64_t)g * kMatchRec, st.m);
   if (KC) {
     st.w0 = words[g];
     st.w1 = words[g + 4];
@@ -196,7 +194,10 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
   static_assert(!KC || kL >= 16, "a lane per distance-cache candidate");
   constexpr uint64_t kLaneMask = kL == 64 ? ~0ull : ((1ull << kL) - 1);
   __shared__ uint32_t ptab_all[kDpWaves * kS][24 * kPtabW];   // per segment: (insert code, copy code) -> fp16 (explicit distance) | fp16 (short code 0) << 16
-  __shared__ uint8_t cctab[kLenTab];                       // length -> copy code
+  // length -> copy code, from length -kL (0 there): the read at the top of a step indexes it
+  // with every lane's length, negative for consumed nodes, without a clamp
+  __shared__ uint8_t cct_all[kL + kLenTab];
+  uint8_t *const cctab = cct_all + kL;
   __shared__ uint16_t itab[kInsTab];                       // insert length -> insert code | its extra bits << 8
   __shared__ uint16_t litc_all[kDpWaves * kS][256];   // literal costs in 1/256 bits (exact: they are quantised so)
   // (one spare entry per 32 lanes, per 16 with four segments: the entries the segments read at
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
   // banks apart instead of on the same banks: 16 entries are 192 words, a multiple of the 64)
   constexpr int kPadSh = KS == 4 ? 4 : 5;
   __shared__ StageEnt stg_all[kDpWaves][64 + (64 >> kPadSh)];
-  for (int t = threadIdx.x; t < kLenTab; t += 64 * kDpWaves) cctab[t] = (uint8_t)(t >= 2 ? copy_code((uint32_t)t) : 0);
+  for (int t = (int)threadIdx.x - kL; t < kLenTab; t += 64 * kDpWaves) cctab[t] = (uint8_t)(t >= 2 ? copy_code((uint32_t)t) : 0);
   for (int t = threadIdx.x; t < kInsTab; t += 64 * kDpWaves) {
     const int ic = ins_code((uint32_t)t);
     itab[t] = (uint16_t)(ic | (ins_extra(ic) << 8));
@@ -330,10 +331,17 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
   uint64_t prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t pt0 = __builtin_amdgcn_s_memtime();
 #endif
+  // kEarly: the four-segment build reads a step's tables at its top and prices a staged
+  // entry's distances together (below).  Its step waits on its chain; the builds with fewer
+  // segments a wave keep the reads where they are needed: they run more waves per SIMD, and the
+  // early reads' address arithmetic cost FONT mode's builds (KR, KC: the most VALU work a step)
+  // more than the shorter chain gave (C3 encode -2 %; C2 and the cadence leg did not move).
+  constexpr bool kEarly = KS == 4;
   // stage the batch starting at i0 (the window's chunk 0 starts there) into this lane's entry
   auto stage = [&]() {
     Staged cur;
-    cur.nm = 0;
+#pragma unroll
+    for (int q = 0; q < kMaxMatches; q++) cur.m[q] = 0;
     cur.lit = 0;
     cur.w0 = cur.w1 = 0;
     if (pf_at == i0) {
@@ -342,17 +350,27 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
       load_staged<KC>(cur, matches, data, pwords, gbase + i0 + hl, i0 + hl);
     }
     const uint32_t nx = i0 + kL;
-    if (nx + hl < b) load_staged<KC>(pf, matches, data, pwords, gbase + nx + hl, nx + hl);
-    pf_at = nx;
+    if constexpr (!kEarly) {
+      if (nx + hl < b) load_staged<KC>(pf, matches, data, pwords, gbase + nx + hl, nx + hl);
+    }
     const uint32_t p = i0 + hl;
-    const uint32_t nm = p < b ? cur.nm : 0u;
+    uint32_t nm = 0;
+#pragma unroll
+    for (int q = 0; q < kMaxMatches; q++) nm += cur.m[q] != 0u;
+    nm = p < b ? nm : 0u;
     StageEnt e;
     e.lc = p < b ? (float)litc[cur.lit] * (1.f / 256.f) : 0.f;
     uint32_t maxlen = 0, word = 0;
+    // (kEarly) the entries' distance codes first, then their symbols' prices together (second
+    // iteration: loads from the stream's CostModel -- one wait for the entry's, not a load and
+    // a wait per match under its branch), then the packed words
+    uint32_t dpq[kMaxMatches];
+    float dsc[kMaxMatches];
 #pragma unroll
     for (int q = 0; q < kMaxMatches; q++) {
       e.m[q] = 0;
       e.mc[q] = 0;
+      dpq[q] = 0;
       if ((uint32_t)q < nm) {
         uint32_t extra;
         uint32_t md = match_dist(cur.m[q]), d = md;
@@ -367,17 +385,78 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
           word = ln == match_length(cur.m[q]) ? 1u : 0u;   // cut by the segment end: unusable
           ln = word ? ln : 0u;
         }
-        const uint32_t dp = dist_prefix(d + 15, ndirect, npostfix, &extra);
+        dpq[q] = dist_prefix(d + 15, ndirect, npostfix, &extra);
         e.m[q] = (ln << 24) | md;
-        const float dc = (float)(dp >> 10) + dist_price(dp & 0x3FFu, cm);
-        e.mc[q] = md | (min((uint32_t)(dc * 4.f + 0.5f), kCostLast - 1) << 24);
+        e.mc[q] = md;
+        if constexpr (!kEarly) {
+          const float dc = (float)(dpq[q] >> 10) + dist_price(dpq[q] & 0x3FFu, cm);
+          e.mc[q] |= min((uint32_t)(dc * 4.f + 0.5f), kCostLast - 1) << 24;
+        }
         maxlen = ln;
       }
     }
+#pragma unroll
+    for (int q = 0; kEarly && q < kMaxMatches; q++) {
+      const uint32_t code = dpq[q] & 0x3FFu;
+      if constexpr (KM) {   // (every lane loads, from its stream's model or the first: no branch)
+        const float v = (cm ? cm : model)->dist[min(code, 127u)];
+        dsc[q] = cm ? v : dist_sym_cost(code);
+      } else {
+        dsc[q] = dist_sym_cost(code);
+      }
+    }
+#pragma unroll
+    for (int q = 0; kEarly && q < kMaxMatches; q++)
+      if ((uint32_t)q < nm) {
+        const float dc = (float)(dpq[q] >> 10) + dsc[q];
+        e.mc[q] |= min((uint32_t)(dc * 4.f + 0.5f), kCostLast - 1) << 24;
+      }
     e.info = (maxlen ? nm : 0u) | (maxlen << 8) | ((word ? maxlen : 2u) << 16);   // | the shortest usable length
     e.w[0] = KC ? cur.w0 : 0u;
     e.w[1] = KC ? cur.w1 : 0u;
     stg[lane + (lane >> kPadSh)] = e;
+    // (kEarly) the next batch's loads last, after every wait above: issued before them, those
+    // waits (for this batch's own loads after a jump, for the model's prices) waited for these too
+    if constexpr (kEarly) {
+      if (nx + hl < b) load_staged<KC>(pf, matches, data, pwords, gbase + nx + hl, nx + hl);
+    }
+    pf_at = nx;
+  };
+  // What a step reads that does not depend on its node -- the stage entry of offset off, and
+  // the copy codes of the lengths l = kL c + hl - off of the first kPre chunks (the chunks a step
+  // of text usually reaches) -- is read at the top of the step, behind the node fetch and without
+  // waiting for it: the step's chain is the fetch, one round of the table reads that need the
+  // node (the insert code's, the price row's), and the relaxation; as reads under the
+  // relaxation's branches it was a round trip to LDS per table and chunk.  (A step ahead, into a
+  // second register set, cost more in the copies than it hid: DESIGN.md section 3m.)
+  constexpr int kPre = kEarly ? 3 : 0;
+  struct StepIn {
+    uint32_t info;
+    float lc;
+    uint32_t m[kMaxMatches], mc[kMaxMatches];
+    uint32_t cc[kPre ? kPre : 1];
+  };
+  auto read_step = [&](uint32_t o) {   // the node-independent inputs of the step at offset o
+    const uint32_t s = hbase + (o & (kL - 1));
+    const StageEnt &e = stg[s + (s >> kPadSh)];
+    StepIn r;
+    r.info = e.info;
+    r.lc = e.lc;
+    if constexpr (kMaxMatches == 4) {
+      const uint4 em = *reinterpret_cast<const uint4 *>(e.m), emc = *reinterpret_cast<const uint4 *>(e.mc);
+      r.m[0] = em.x; r.m[1] = em.y; r.m[2] = em.z; r.m[3] = em.w;
+      r.mc[0] = emc.x; r.mc[1] = emc.y; r.mc[2] = emc.z; r.mc[3] = emc.w;
+    } else {
+#pragma unroll
+      for (int q = 0; q < kMaxMatches; q++) {
+        r.m[q] = e.m[q];
+        r.mc[q] = e.mc[q];
+      }
+    }
+    const int l0 = (int)hl - (int)o;   // (>= -kL: o < kL)
+#pragma unroll
+    for (int c = 0; c < kPre; c++) r.cc[c] = cctab[l0 + kL * c];
+    return r;
   };
   if (!done) stage();
   wave_sync();
@@ -389,6 +468,8 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
     const uint32_t src = hbase + (off & (kL - 1));
     const float ci = __uint_as_float(bperm(src, __float_as_uint(wc[0])));
     const uint32_t ld = bperm(src, wd[0]), mm = bperm(src, wm[0]);
+    if constexpr (kEarly) __builtin_amdgcn_sched_barrier(0);   // (the fetch first: LDS returns in issue order)
+    const StepIn e = read_step(off);
     if (!done) {
       chd = hl == off ? ld : chd;
       chm = hl == off ? mm : chm;
@@ -399,7 +480,6 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
       }
     }
     const bool act = !done;
-    const StageEnt &e = stg[src + (src >> kPadSh)];
     const uint32_t info = e.info;
     const uint32_t nm = act ? (info & 0xFF) : 0u, maxlen = act ? ((info >> 8) & 0xFF) : 0u;
     const uint32_t minlen = info >> 16;   // 2, or a dictionary word's length: that length only
@@ -409,13 +489,18 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
     // nx); a copy's end node has none
     const int ic = ins ? (int)(mm & 0xFF) : 0;
     const uint32_t iextra = ins ? (mm >> 8) & 0xFF : 0u;
-    // the codes of insert length ins + 1, for the literal edge out of i: looked up now, beside
-    // the copy prices' lookup, so the next step has no insert-code lookup on its serial path
+    // the reads that need the node, issued together, one wait for all of them: the codes of
+    // insert length ins + 1, for the literal edge out of i (looked up now, so the next step has
+    // no insert-code lookup on its serial path), and the first kPre chunks' copy prices from the
+    // insert code's row (read whether or not the step reaches the chunk: a read costs less than
+    // the branch and the second wait that skipping it did)
     const uint32_t ins1 = min(ins + 1, 65535u);
-    uint32_t nx;
-    if (__builtin_expect(ins1 < (uint32_t)kInsTab, 1)) {
-      nx = itab[ins1];
-    } else {
+    const uint32_t *trow = ptab + ic * kPtabW;
+    uint32_t nx = itab[min(ins1, (uint32_t)kInsTab - 1u)];
+    uint32_t tvp[kPre ? kPre : 1];
+#pragma unroll
+    for (int c = 0; c < kPre; c++) tvp[c] = trow[e.cc[c]];
+    if (__builtin_expect(ins1 >= (uint32_t)kInsTab, 0)) {
       const int c1 = ins_code_sel(ins1);
       nx = (uint32_t)c1 | (ins_extra_sel(c1) << 8);
     }
@@ -495,20 +580,12 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
       continue;
     }
     // the match staircase of i: lengths (clipped) and the packed (distance | cost code) words
-    // (both read unconditionally: a masked load would be a branch and a wait per entry)
     const uint32_t actm = 0u - (uint32_t)act;
     uint32_t mL[kMaxMatches], vpk[kMaxMatches];
-    if constexpr (kMaxMatches == 4) {
-      const uint4 em = *reinterpret_cast<const uint4 *>(e.m), emc = *reinterpret_cast<const uint4 *>(e.mc);
-      mL[0] = match_length(em.x) & actm; mL[1] = match_length(em.y) & actm;   // 0 past nm
-      mL[2] = match_length(em.z) & actm; mL[3] = match_length(em.w) & actm;
-      vpk[0] = emc.x; vpk[1] = emc.y; vpk[2] = emc.z; vpk[3] = emc.w;
-    } else {
 #pragma unroll
-      for (int q = 0; q < kMaxMatches; q++) {
-        mL[q] = match_length(e.m[q]) & actm;
-        vpk[q] = e.mc[q];
-      }
+    for (int q = 0; q < kMaxMatches; q++) {
+      mL[q] = match_length(e.m[q]) & actm;   // 0 past nm
+      vpk[q] = e.mc[q];
     }
     // the last-distance copy out of node i - 1 (see rp_d): its length R from the loaded bytes
     uint32_t R = 0;
@@ -521,9 +598,11 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
       R = R >= 2 ? R : 0u;
     }
     const uint32_t maxrel = max(max(1u, maxlen), R ? R - 1 : 0u);
-    const uint32_t *trow = ptab + ic * kPtabW;
 
-    // relax every edge out of i: lane j of chunk k takes length kL k + j - off
+    // relax every edge out of i: lane j of chunk k takes length kL k + j - off.  A chunk's copy
+    // prices stay under the range test (most steps of text have no match: the masked form skips
+    // their arithmetic, and the step is bound by VALU issue as much as by its chain); the reads
+    // they need are done, so no wait stands inside.
 #pragma unroll
     for (int c = 0; c < kC; c++) {
       if (c > 0 && __ballot(act && (uint32_t)(kL * c) <= off + maxrel) == 0) break;
@@ -536,7 +615,7 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
 #pragma unroll
         for (int q = kMaxMatches - 1; q >= 0; q--)
           x = l <= mL[q] ? vpk[q] : x;   // mL = 0 past nm
-        const uint32_t tv = trow[cctab[l]];
+        const uint32_t tv = c < kPre ? tvp[c] : trow[cctab[l]];
         const float pn = (float)__builtin_bit_cast(_Float16, (uint16_t)(tv & 0xFFFF));
         const float pl = (float)__builtin_bit_cast(_Float16, (uint16_t)(tv >> 16));
         nd = match_dist(x);
