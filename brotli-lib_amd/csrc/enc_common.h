@@ -524,7 +524,8 @@ void launch_cost_model(hipStream_t st, const Job *jobs, int njobs, const Seg *se
                        uint32_t *hist, CostModel *model);
 void launch_dp(hipStream_t st, const Job *jobs, const Seg *segs, int nsegs, const uint32_t *lit_h, const CostModel *model,
                const uint32_t *matches, uint64_t *choice, bool cdict, bool font, const uint32_t *words, uint32_t *ring_hist,
-               const Mb *mbs);
+               const Mb *mbs, int piece_shift);
+void dp_launch_counts(unsigned long long out[4]);   // dp_kernel launches by pieces a wave: 1, 2, 4, 8
 size_t dp_ring_hist_bytes(int nsegs);
 void launch_any_binary(hipStream_t st, const Job *jobs, int njobs, uint32_t *flag);
 void launch_words(hipStream_t st, const Job *jobs, const uint32_t *pos_job, const SegRef *seg_ref, uint32_t total, uint32_t *words);

@@ -71,6 +71,11 @@ constexpr int kDpWavesPerSimd = MIB_DP_OCC;
 #ifndef MIB_DP_OCC_KS4
 #define MIB_DP_OCC_KS4 MIB_DP_OCC   // (A/B builds: the four-segment build's occupancy target)
 #endif
+// the eight-piece build: window chunks in registers (lengths to 95 - off; the other 14 chunks'
+// ring in LDS, with the block's tables 52.9 KB: three blocks a CU, 160 VGPRs: three waves a
+// SIMD), and the chunks of 8 lanes a step's early reads cover (lengths to 31 - off)
+constexpr int kNear8 = 12;
+constexpr int kPre8 = 4;
 constexpr int kPtabW = 20;
 constexpr int kRepLen = 16;   // last-distance copies relaxed up to this length (<= the lanes per segment)
 static_assert(kLongCopy <= 325, "copy codes of lengths <= 325 are < 20 (command.ts getCopyLengthCode)");
@@ -179,32 +184,51 @@ static_assert(kHistPos > (uint32_t)kLongCopy, "a copy's predecessor must still b
 // kCDictMark; a separate build, so the common case pays nothing for it).  KR: the parse relaxes
 // last-distance copies (rp_d below; FONT mode: C3 -1 % bytes, text -0.1 %, a separate build so
 // text pays nothing for it)
+// KS 8: the wave's eight lane groups parse pieces of ONE segment (launch_dp: the call parses
+// pieces and every segment has at least eight of them, consecutive in the piece table from a
+// multiple of eight), so one price table and one literal-cost table serve the wave (KW below),
+// filled by all 64 lanes: 2.4 KB a wave where a table per lane group would take 19.5 KB.
 template <int KS, bool KM, bool KD, bool KR, bool KC>
-__global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS == 2) ? 3 : kDpWavesPerSimd) void dp_kernel(const Job *jobs, const Seg *segs, int nsegs,
+__global__ __launch_bounds__(64 * kDpWaves, KS == 8 ? 3 : KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS == 2) ? 3 : kDpWavesPerSimd) void dp_kernel(const Job *jobs, const Seg *segs, int nsegs,
                                                            const uint32_t *lit_histo, const CostModel *model,
                                                            const uint32_t *matches,
                                                            uint64_t *choice /* per position+1 */, float cmd_pen, int use_rep,
                                                            const uint32_t *pwords, uint32_t *ring_hist, const Mb *mbs,
                                                            int kc_split) {
   constexpr int kS = KS;                // segments per wave
+  constexpr bool KW = KS == 8;          // one price table and one literal-cost table per wave
   constexpr int kL = 64 / kS;           // lanes per segment
   constexpr int kC = (kL - 1 + kLongCopy) / kL + 1;   // chunks: batch offset (< kL) + longest relaxed length
   static_assert(kL - 1 + kLongCopy < kL * kC, "every relaxed length must land in a chunk");
-  static_assert(kRepLen <= kL, "a last-distance copy is measured by one lane per byte");
+  // Eight pieces a wave keep the first kW chunks of the window in registers (text's staircases
+  // end well inside them) and the far chunks, up to length kLongCopy, in LDS: a ring of kFar
+  // slots per lane, slot (fbase + c - kW) % kFar holding chunk c's node as cost | distance |
+  // length << 24 (a far node is a copy's end: a window distance below 2^24, a length <= 200).
+  // At a batch end the top register chunk takes the ring's first slot, which becomes the new
+  // last chunk.  A node receives the candidates it received in registers, in the same order.
+  constexpr int kW = KS == 8 ? kNear8 : kC;   // chunks in registers
+  constexpr int kFar = kC - kW;
+  static_assert(KS == 8 || kFar == 0, "the other builds keep the whole window in registers");
+  static_assert(!KR || kRepLen <= kL, "a last-distance copy is measured by one lane per byte");
+  static_assert(KS < 8 || (!KD && !KR && !KC), "eight pieces a wave: the plain build only");
+  constexpr int kT = KW ? 1 : kS;       // price / literal-cost tables per wave
   static_assert(!KC || kL >= 16, "a lane per distance-cache candidate");
   constexpr uint64_t kLaneMask = kL == 64 ? ~0ull : ((1ull << kL) - 1);
-  __shared__ uint32_t ptab_all[kDpWaves * kS][24 * kPtabW];   // per segment: (insert code, copy code) -> fp16 (explicit distance) | fp16 (short code 0) << 16
+  __shared__ uint32_t ptab_all[kDpWaves * kT][24 * kPtabW];   // per segment: (insert code, copy code) -> fp16 (explicit distance) | fp16 (short code 0) << 16
   // length -> copy code, from length -kL (0 there): the read at the top of a step indexes it
   // with every lane's length, negative for consumed nodes, without a clamp
   __shared__ uint8_t cct_all[kL + kLenTab];
   uint8_t *const cctab = cct_all + kL;
   __shared__ uint16_t itab[kInsTab];                       // insert length -> insert code | its extra bits << 8
-  __shared__ uint16_t litc_all[kDpWaves * kS][256];   // literal costs in 1/256 bits (exact: they are quantised so)
+  __shared__ uint16_t litc_all[kDpWaves * kT][256];   // literal costs in 1/256 bits (exact: they are quantised so)
   // (one spare entry per 32 lanes, per 16 with four segments: the entries the segments read at
   // the same offset in one instruction -- i and 32 + i, or i, 16 + i, 32 + i, 48 + i -- fall 12
-  // banks apart instead of on the same banks: 16 entries are 192 words, a multiple of the 64)
-  constexpr int kPadSh = KS == 4 ? 4 : 5;
+  // banks apart instead of on the same banks: 16 entries are 192 words, a multiple of the 64;
+  // with eight segments one per 8 lanes: 9 entries are 108 words, and the eight b128 reads of
+  // a step start at words 0, 44, 24, 4, 48, 28, 8, 52 of the 64)
+  constexpr int kPadSh = KS == 8 ? 3 : KS == 4 ? 4 : 5;
   __shared__ StageEnt stg_all[kDpWaves][64 + (64 >> kPadSh)];
+  __shared__ uint2 far_all[kDpWaves][kFar ? kFar * 64 : 1];
   for (int t = (int)threadIdx.x - kL; t < kLenTab; t += 64 * kDpWaves) cctab[t] = (uint8_t)(t >= 2 ? copy_code((uint32_t)t) : 0);
   for (int t = threadIdx.x; t < kInsTab; t += 64 * kDpWaves) {
     const int ic = ins_code((uint32_t)t);
@@ -215,8 +239,8 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
   const uint32_t h = lane / kL, hl = lane % kL, hbase = h * kL;
   const int sgi = (blockIdx.x * kDpWaves + (int)w) * kS + (int)h;
   StageEnt *stg = stg_all[w];
-  uint16_t *litc = litc_all[w * kS + h];
-  uint32_t *ptab = ptab_all[w * kS + h];
+  uint16_t *litc = litc_all[KW ? w : w * kS + h];
+  uint32_t *ptab = ptab_all[KW ? w : w * kS + h];
   // this lane group's segment (a = b: nothing to parse)
   uint32_t a = 0, b = 0, gbase = 0, job = 0;
   const uint8_t *data = nullptr;
@@ -251,28 +275,42 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
   // stream's CostModel (per segment tables: a wave's segments may be different streams)
   const CostModel *cm = (KM && a < b) ? model + job : nullptr;
   const float dist0 = dist_price(0, cm);
-  if (a < b)
-    for (uint32_t t = hl; t < 24 * kPtabW; t += kL) {
+  // the tables' filler: a lane group for its own segment, or (KW) the whole wave for the one
+  // segment its groups share -- the stream of the first group with a piece to parse (a segment's
+  // last pieces may be empty)
+  constexpr uint32_t kF = KW ? 64u : (uint32_t)kL;   // lanes filling a table
+  const uint32_t tl = KW ? lane : hl;
+  uint32_t fjob = job;
+  bool fill = a < b;
+  if constexpr (KW) {
+    // (some lane has a < b: the wave returned above otherwise, so the ballot has a bit set)
+    fjob = (uint32_t)__builtin_amdgcn_readlane((int)job, (int)__ffsll((unsigned long long)__ballot(a < b)) - 1);
+    fill = true;
+  }
+  const CostModel *cmf = KW ? (KM ? model + fjob : nullptr) : cm;
+  const float dist0f = KW ? dist_price(0, cmf) : dist0;
+  if (fill)
+    for (uint32_t t = tl; t < 24 * kPtabW; t += kF) {
       const int ic = (int)(t / kPtabW), cc = (int)(t % kPtabW);
-      const _Float16 x = (_Float16)(copy_price(ic, cc, false, dist0, cm) + cmd_pen),
-                     y = (_Float16)(copy_price(ic, cc, true, dist0, cm) + cmd_pen);
+      const _Float16 x = (_Float16)(copy_price(ic, cc, false, dist0f, cmf) + cmd_pen),
+                     y = (_Float16)(copy_price(ic, cc, true, dist0f, cmf) + cmd_pen);
       ptab[t] = (uint32_t)__builtin_bit_cast(uint16_t, x) | ((uint32_t)__builtin_bit_cast(uint16_t, y) << 16);
     }
   // literal costs: iteration 0 from the stream's order-0 histogram (zopfli-cost-model.ts:
   // 163-189), iteration 1 from the model
-  if (cm) {
-    if (a < b)
-      for (uint32_t k = hl; k < 256; k += kL)
-        litc[k] = (uint16_t)(uint32_t)(fminf(fmaxf(cm->lit[k], 1.f), 255.f) * 256.f);
+  if (cmf) {
+    if (fill)
+      for (uint32_t k = tl; k < 256; k += kF)
+        litc[k] = (uint16_t)(uint32_t)(fminf(fmaxf(cmf->lit[k], 1.f), 255.f) * 256.f);
   } else {
     uint32_t part = 0;
-    if (a < b)
-      for (uint32_t k = hl; k < 256; k += kL) part += lit_histo[job * 256 + k];
-    for (int o = kL / 2; o; o >>= 1) part += __shfl_xor(part, o);
+    if (fill)
+      for (uint32_t k = tl; k < 256; k += kF) part += lit_histo[fjob * 256 + k];
+    for (int o = (int)kF / 2; o; o >>= 1) part += __shfl_xor(part, o);
     const float lt = log2f((float)max(part, 1u));
-    if (a < b)
-      for (uint32_t k = hl; k < 256; k += kL) {
-        const uint32_t c = lit_histo[job * 256 + k];
+    if (fill)
+      for (uint32_t k = tl; k < 256; k += kF) {
+        const uint32_t c = lit_histo[fjob * 256 + k];
         const float v = c ? lt - log2f((float)c) : lt + 2.f;
         litc[k] = (uint16_t)(uint32_t)(fminf(fmaxf(v, 1.f), 255.f) * 256.f);
       }
@@ -280,13 +318,19 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
   wave_sync();
   // the pending nodes: cost, last distance, and the copy length that reached it, or (a literal
   // edge) insert length << 16 | its insert code | the code's extra bits << 8
-  float wc[kC];
-  uint32_t wd[kC], wm[kC];
+  float wc[kW];
+  uint32_t wd[kW], wm[kW];
 #pragma unroll
-  for (int c = 0; c < kC; c++) {
+  for (int c = 0; c < kW; c++) {
     wc[c] = kInf;
     wd[c] = wm[c] = 0;
   }
+  uint2 *const far = far_all[w] + lane;   // (this lane's column: slot s at far[64 s])
+  uint32_t fbase = 0;
+  auto far_clear = [&]() {
+    for (int s2 = 0; s2 < kFar; s2++) far[64 * s2] = make_uint2(__float_as_uint(kInf), 0u);
+  };
+  if constexpr (kFar > 0) far_clear();
   if (hl == 0) wc[0] = 0.f;   // node a
   Staged pf;
   uint32_t pf_at = a;
@@ -331,12 +375,12 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
   uint64_t prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t pt0 = __builtin_amdgcn_s_memtime();
 #endif
-  // kEarly: the four-segment build reads a step's tables at its top and prices a staged
-  // entry's distances together (below).  Its step waits on its chain; the builds with fewer
+  // kEarly: the four- and eight-segment builds read a step's tables at their top and prices a staged
+  // entry's distances together (below).  Their step waits on its chain; the builds with fewer
   // segments a wave keep the reads where they are needed: they run more waves per SIMD, and the
   // early reads' address arithmetic cost FONT mode's builds (KR, KC: the most VALU work a step)
   // more than the shorter chain gave (C3 encode -2 %; C2 and the cadence leg did not move).
-  constexpr bool kEarly = KS == 4;
+  constexpr bool kEarly = KS >= 4;
   // stage the batch starting at i0 (the window's chunk 0 starts there) into this lane's entry
   auto stage = [&]() {
     Staged cur;
@@ -429,7 +473,7 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
   // node (the insert code's, the price row's), and the relaxation; as reads under the
   // relaxation's branches it was a round trip to LDS per table and chunk.  (A step ahead, into a
   // second register set, cost more in the copies than it hid: DESIGN.md section 3m.)
-  constexpr int kPre = kEarly ? 3 : 0;
+  constexpr int kPre = KS == 8 ? kPre8 : kEarly ? 3 : 0;
   struct StepIn {
     uint32_t info;
     float lc;
@@ -567,7 +611,8 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
         i0 = i;
         rp_d = 0;
 #pragma unroll
-        for (int c = 0; c < kC; c++) wc[c] = kInf;
+        for (int c = 0; c < kW; c++) wc[c] = kInf;
+        if constexpr (kFar > 0) far_clear();
         if (hl == 0) {
           wc[0] = fc;
           wd[0] = fd;
@@ -604,7 +649,7 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
     // their arithmetic, and the step is bound by VALU issue as much as by its chain); the reads
     // they need are done, so no wait stands inside.
 #pragma unroll
-    for (int c = 0; c < kC; c++) {
+    for (int c = 0; c < kW; c++) {
       if (c > 0 && __ballot(act && (uint32_t)(kL * c) <= off + maxrel) == 0) break;
       const uint32_t l = (uint32_t)(kL * c) + hl - off;   // wraps (huge) for consumed nodes
       float cand = kInf;
@@ -632,12 +677,37 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
         wm[c] = nmeta;
       }
     }
+    if constexpr (kFar > 0) {
+      // the far chunks (rare: a match of 90 bytes or more): the same candidates into the ring
+      if (__ballot(act && (uint32_t)(kL * kW) <= off + maxrel)) {
+        for (int c = kW; c < kC; c++) {
+          if (__ballot(act && (uint32_t)(kL * c) <= off + maxrel) == 0) break;
+          const uint32_t l = (uint32_t)(kL * c) + hl - off;
+          if (l >= minlen && l <= maxlen) {
+            uint32_t x = 0;
+#pragma unroll
+            for (int q = kMaxMatches - 1; q >= 0; q--)
+              x = l <= mL[q] ? vpk[q] : x;
+            const uint32_t tv = trow[cctab[l]];
+            const float pn = (float)__builtin_bit_cast(_Float16, (uint16_t)(tv & 0xFFFF));
+            const float pl = (float)__builtin_bit_cast(_Float16, (uint16_t)(tv >> 16));
+            const uint32_t nd = match_dist(x);
+            const float alt = __builtin_fmaf((float)(x >> 24), 0.25f, pn);
+            const float cand = base + (nd == ld ? pl : alt);
+            uint32_t s2 = fbase + (uint32_t)(c - kW);
+            s2 = s2 >= (uint32_t)kFar ? s2 - (uint32_t)kFar : s2;
+            const uint2 cur = far[64 * s2];
+            if (cand < __uint_as_float(cur.x)) far[64 * s2] = make_uint2(__float_as_uint(cand), nd | (l << 24));
+          }
+        }
+      }
+    }
     if (KR && __ballot(R != 0)) {
       // the last-distance copies of lengths 2 .. R <= kRepLen out of node i - 1: lane j of chunk
       // c holds length kL c + j - off + 1 (chunks 0 and 1 hold them all)
       const uint32_t *rrow = ptab + rp_ic * kPtabW;
 #pragma unroll
-      for (int c = 0; c < 2 && c < kC; c++) {
+      for (int c = 0; c < 2 && c < kW; c++) {
         const uint32_t lr = (uint32_t)(kL * c) + hl - off + 1u;   // wraps (huge) below the node
         if (lr >= 2u && lr <= R) {
           const uint32_t tv = rrow[cctab[lr]];
@@ -688,9 +758,9 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
         const uint32_t *crow = ptab + ((kf >> 16) & 0xFFu) * kPtabW;
         // (only the chunks some passing candidate reaches: one ballot a chunk; all kC chunks'
         // lookups unconditionally were 88 of the section's instructions, r06 ISA listing)
-        uint32_t ctv[kC];
+        uint32_t ctv[kW];
 #pragma unroll
-        for (int c = 0; c < kC; c++) {
+        for (int c = 0; c < kW; c++) {
           ctv[c] = 0u;
           if (c > 1 && __ballot(pass && (uint32_t)(kL * c) + 2u <= off + R) == 0) break;
           const uint32_t lr = (uint32_t)(kL * c) + hl + 2u - off;   // wraps (huge) below node i-2
@@ -706,7 +776,7 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
           const uint32_t Rk = mine ? bperm(src, R) : 0u, dk = bperm(src, cq_d);
           const float ck = __uint_as_float(bperm(src, __float_as_uint(ccost)));   // short code k's distance symbol
 #pragma unroll
-          for (int c = 0; c < kC; c++) {
+          for (int c = 0; c < kW; c++) {
             if (c > 1 && __ballot((uint32_t)(kL * c) + 2u <= off + Rk) == 0) break;
             const uint32_t lr = (uint32_t)(kL * c) + hl + 2u - off;
             if (lr >= 4u && lr <= Rk) {
@@ -777,15 +847,39 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 4 ? MIB_DP_OCC_KS4 : (KC && KS
       // batch end: the window moves down one chunk -- by selects of the whole wave, outside the
       // divergent branch (as moves under the branch, the register allocator copied the window
       // back and forth on every step instead, ~25 moves a step, r05 ISA listing)
+      uint32_t bmask = bend ? ~0u : 0u;
+      if constexpr (KW) asm("" : "+v"(bmask));
 #pragma unroll
-      for (int c = 0; c + 1 < kC; c++) {
-        wc[c] = bend ? wc[c + 1] : wc[c];
-        wd[c] = bend ? wd[c + 1] : wd[c];
-        wm[c] = bend ? wm[c + 1] : wm[c];
+      for (int c = 0; c + 1 < kW; c++) {
+        if constexpr (KW) {
+          // (a bit select under a mask the optimiser cannot see through: in these builds it
+          // otherwise turns the select of two elements into an element at a selected INDEX, and
+          // the window leaves the registers for a dynamically indexed array -- 2,180 selects in
+          // the eight-piece build's listing; v_bfi_b32, one instruction as the select is)
+          wc[c] = __uint_as_float((__float_as_uint(wc[c + 1]) & bmask) | (__float_as_uint(wc[c]) & ~bmask));
+          wd[c] = (wd[c + 1] & bmask) | (wd[c] & ~bmask);
+          wm[c] = (wm[c + 1] & bmask) | (wm[c] & ~bmask);
+        } else {
+          wc[c] = bend ? wc[c + 1] : wc[c];
+          wd[c] = bend ? wd[c + 1] : wd[c];
+          wm[c] = bend ? wm[c + 1] : wm[c];
+        }
       }
-      wc[kC - 1] = bend ? kInf : wc[kC - 1];
-      wd[kC - 1] = bend ? 0u : wd[kC - 1];
-      wm[kC - 1] = bend ? 0u : wm[kC - 1];
+      if constexpr (kFar > 0) {
+        // the top register chunk takes the ring's first slot; the slot is the new last chunk
+        const uint2 nxt = far[64 * fbase];
+        wc[kW - 1] = bend ? __uint_as_float(nxt.x) : wc[kW - 1];
+        wd[kW - 1] = bend ? (nxt.y & 0xFFFFFFu) : wd[kW - 1];
+        wm[kW - 1] = bend ? (nxt.y >> 24) : wm[kW - 1];
+        if (bend) {
+          far[64 * fbase] = make_uint2(__float_as_uint(kInf), 0u);
+          fbase = fbase + 1u == (uint32_t)kFar ? 0u : fbase + 1u;
+        }
+      } else {
+        wc[kC - 1] = bend ? kInf : wc[kC - 1];
+        wd[kC - 1] = bend ? 0u : wd[kC - 1];
+        wm[kC - 1] = bend ? 0u : wm[kC - 1];
+      }
       if (bend) {
         // store the batch's choices, stage the next batch
         if (i0 + hl != a) choice[gbase + i0 + hl] = choice_of(chd, chm);   // node a belongs to the previous segment
@@ -1340,25 +1434,48 @@ extern "C" int mib_debug_read_dp_prof(unsigned long long *out) {
 // r04an; in round 3, before the LDS trim, it was slower: 106.6 -> 119.5 ms)
 // FONT mode keeps two: its longer staircases need more of the 16-lane chunks a step (C3 dp
 // 38.4 -> 46.6 ms beside the other encode lane, r04ao).
+// Eight pieces a wave (8 lanes each): the plain build (no FONT mode, candidates or custom
+// dictionary) of a call whose pieces come at least eight to a segment (piece_shift >= 3: a wave
+// then parses one segment, dp_kernel KW), from kKs8Segs pieces on: about half of a step's
+// instructions do not depend on how many pieces share the wave (C4's second pass 16.9 -> 12.3 G
+// VALU a half-batch launch, 36.2 -> 30.3 ms alone, 62.7 -> 41.7 ms beside the other lane; with
+// the whole window in registers, 252 VGPRs and two waves a SIMD, it lost 0.7 % of C4:
+// DESIGN.md section 3m).
 constexpr int kKs4Segs = 3 * 4 * 1024;
-static int dp_ks(int nsegs, bool font) {
+// kKs8Segs by measurement on C4's shape (1 MiB text streams, 8 KiB pieces, two lanes; encode MB/s,
+// the rule's two pieces a wave against eight): 8,704 pieces a lane 4,645 -> 5,001, 10,240 4,775 ->
+// 4,987, 11,776 4,930 -> 5,280.  Not lower: nothing below 8,704 was measured, and C2's 8,192
+// pieces keep the two-piece build.
+constexpr int kKs8Segs = 8704;
+static int dp_ks(int nsegs, bool font, bool plain, int piece_shift) {
   static const int v = knob("MIB_DP_KS") ? atoi(knob("MIB_DP_KS")) : 0;   // experiments
+  const bool can8 = !font && plain && piece_shift >= 3;
+  if (v == 8 && can8) return 8;   // (a launch that cannot take eight follows the rule)
   if (v == 1 || v == 2 || v == 4) return v;
+  if (can8 && nsegs >= kKs8Segs) return 8;
   return !font && nsegs >= kKs4Segs ? 4 : nsegs <= 2048 ? 1 : 2;
 }
+// piece_shift: the call parses pieces and every segment has at least 2^piece_shift of them,
+// consecutive in the table from a multiple of that (launch_dp); 0: whole segments, or unknown
+// Diagnostic (tests): dp_kernel launches of this process by pieces a wave (1, 2, 4, 8)
+static unsigned long long g_dp_launches[4];
 template <bool KD, bool KC>
 static void launch_dp_t(hipStream_t st, const Job *jobs, const Seg *segs, int nsegs, const uint32_t *lit_h,
                         const CostModel *model, const uint32_t *matches, uint64_t *choice, bool font,
-                        const uint32_t *words, uint32_t *ring_hist, const Mb *mbs, int kc_split) {
-  const int ks = dp_ks(nsegs, font), spw = kDpWaves * ks;
-  const dim3 g((nsegs + spw - 1) / spw), b(64 * kDpWaves);
-  // MIB_CMD_PENALTY (bits, experiment): added to every copy's price, fewer and longer commands
-  static const float cmd_pen = knob("MIB_CMD_PENALTY") ? (float)atof(knob("MIB_CMD_PENALTY")) : 0.f;
+                        const uint32_t *words, uint32_t *ring_hist, const Mb *mbs, int kc_split, int piece_shift) {
   // last-distance candidates in the parse: FONT mode (MIB_DP_REP, experiments: 0 off, 2 every mode)
   static const int rep_knob = knob("MIB_DP_REP") ? atoi(knob("MIB_DP_REP")) : 1;
   const bool rep = rep_knob == 2 || (rep_knob == 1 && font);
+  const bool plain = !KD && !KC && !rep;
+  const int ks = dp_ks(nsegs, font, plain, piece_shift), spw = kDpWaves * ks;
+  const dim3 g((nsegs + spw - 1) / spw), b(64 * kDpWaves);
+  __atomic_fetch_add(&g_dp_launches[ks == 8 ? 3 : ks == 4 ? 2 : ks == 2 ? 1 : 0], 1ull, __ATOMIC_RELAXED);
+  // MIB_CMD_PENALTY (bits, experiment): added to every copy's price, fewer and longer commands
+  static const float cmd_pen = knob("MIB_CMD_PENALTY") ? (float)atof(knob("MIB_CMD_PENALTY")) : 0.f;
 #define MIB_DP(K, M, R) \
   hipLaunchKernelGGL((dp_kernel<K, M, KD, R, KC>), g, b, 0, st, jobs, segs, nsegs, lit_h, model, matches, choice, cmd_pen, 1, words, ring_hist, mbs, kc_split)
+#define MIB_DP_8(M) \
+  hipLaunchKernelGGL((dp_kernel<8, M, false, false, false>), g, b, 0, st, jobs, segs, nsegs, lit_h, model, matches, choice, cmd_pen, 1, words, ring_hist, mbs, kc_split)
 #define MIB_DP_KS(K)                \
   do {                              \
     if (model && rep) MIB_DP(K, true, true);   \
@@ -1366,10 +1483,14 @@ static void launch_dp_t(hipStream_t st, const Job *jobs, const Seg *segs, int ns
     else if (rep) MIB_DP(K, false, true);      \
     else MIB_DP(K, false, false);              \
   } while (0)
-  if (ks == 1) MIB_DP_KS(1);
+  if (ks == 8) {
+    if (model) MIB_DP_8(true);
+    else MIB_DP_8(false);
+  } else if (ks == 1) MIB_DP_KS(1);
   else if (ks == 4) MIB_DP_KS(4);
   else MIB_DP_KS(2);
 #undef MIB_DP_KS
+#undef MIB_DP_8
 #undef MIB_DP
 }
 // (words, ring_hist: the distance-cache candidates' inputs, dp_ring_hist_bytes; null: none).
@@ -1377,15 +1498,18 @@ static void launch_dp_t(hipStream_t st, const Job *jobs, const Seg *segs, int ns
 // are not UTF-8 text, the plain build for the rest (mbs[].ctx_mode must be set).
 void launch_dp(hipStream_t st, const Job *jobs, const Seg *segs, int nsegs, const uint32_t *lit_h, const CostModel *model,
                const uint32_t *matches, uint64_t *choice, bool cdict, bool font, const uint32_t *words, uint32_t *ring_hist,
-               const Mb *mbs) {
+               const Mb *mbs, int piece_shift) {
   const bool kc = words && ring_hist && mbs;
   if (cdict) {
-    if (kc) launch_dp_t<true, true>(st, jobs, segs, nsegs, lit_h, model, matches, choice, font, words, ring_hist, mbs, 1);
-    launch_dp_t<true, false>(st, jobs, segs, nsegs, lit_h, model, matches, choice, font, words, ring_hist, mbs, kc ? 1 : 0);
+    if (kc) launch_dp_t<true, true>(st, jobs, segs, nsegs, lit_h, model, matches, choice, font, words, ring_hist, mbs, 1, piece_shift);
+    launch_dp_t<true, false>(st, jobs, segs, nsegs, lit_h, model, matches, choice, font, words, ring_hist, mbs, kc ? 1 : 0, piece_shift);
   } else {
-    if (kc) launch_dp_t<false, true>(st, jobs, segs, nsegs, lit_h, model, matches, choice, font, words, ring_hist, mbs, 1);
-    launch_dp_t<false, false>(st, jobs, segs, nsegs, lit_h, model, matches, choice, font, words, ring_hist, mbs, kc ? 1 : 0);
+    if (kc) launch_dp_t<false, true>(st, jobs, segs, nsegs, lit_h, model, matches, choice, font, words, ring_hist, mbs, 1, piece_shift);
+    launch_dp_t<false, false>(st, jobs, segs, nsegs, lit_h, model, matches, choice, font, words, ring_hist, mbs, kc ? 1 : 0, piece_shift);
   }
+}
+void dp_launch_counts(unsigned long long out[4]) {
+  for (int q = 0; q < 4; q++) out[q] = __atomic_load_n(&g_dp_launches[q], __ATOMIC_RELAXED);
 }
 size_t dp_ring_hist_bytes(int nsegs) { return (size_t)std::max(nsegs, 1) * kHistPos * 16; }
 // words[g] = the four stream bytes at global position g (0 past the stream's end): the

@@ -365,6 +365,10 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
   std::vector<uint32_t> seg_job;   // per 64 KiB of global positions: its stream
   std::vector<SegRef> seg_ref;     // ... and where its bytes are
   uint64_t pos_total = 0, out_scratch = 0, cmd_total = 0, npieces = 0;
+  // the smallest piece shift of the call's segments: every segment's first piece index is a sum
+  // of earlier segments' 2^shift, so a multiple of 2^min_pshift, and its pieces follow it -- any
+  // 2^min_pshift (or fewer, a power of two) pieces aligned at their count lie in one segment
+  int min_pshift = kMaxPieceShift;
   bool any_hist = false, any_parts = false, any_dict = false, any_cdict = false;
   for (size_t j = 0; j < k; j++) {
     Job &jb = jobs[j];
@@ -439,6 +443,7 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
           const int pshift = dp_piece_shift(n, sd[j].streaming);
           sg.pieces = (uint32_t)(npieces << 3) | (uint32_t)pshift;
           npieces += 1ull << pshift;
+          min_pshift = std::min(min_pshift, pshift);
           segs.push_back(sg);
         }
         mb.nseg = (uint32_t)segs.size() - mb.first_seg;
@@ -630,7 +635,8 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
     tm.start(two_pass ? "dp_sample" : "dp_parse");
     Seg *s1 = sampled ? d_sample : two_pass ? d_segs : d_fin;
     const int n1 = s1 == d_fin ? nfin : nsegs;
-    launch_dp(st, d_jobs, s1, n1, lit_h, nullptr, matches, choice, any_cdict, prm.font, pos_words, ring_hist, d_mbs);
+    launch_dp(st, d_jobs, s1, n1, lit_h, nullptr, matches, choice, any_cdict, prm.font, pos_words, ring_hist, d_mbs,
+              s1 == d_fin && ps ? min_pshift : 0);
     tm.stop();
     tm.start("backtrack");
     launch_backtrack(st, d_jobs, s1, n1, choice, raw);
@@ -640,7 +646,8 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
       launch_cost_model(st, d_jobs, (int)k, s1, nsegs, raw, model_h, model);
       tm.stop();
       tm.start("dp_parse");
-      launch_dp(st, d_jobs, d_fin, nfin, lit_h, model, matches, choice, any_cdict, prm.font, pos_words, ring_hist, d_mbs);
+      launch_dp(st, d_jobs, d_fin, nfin, lit_h, model, matches, choice, any_cdict, prm.font, pos_words, ring_hist, d_mbs,
+                ps ? min_pshift : 0);
       tm.stop();
       tm.start("backtrack");
       launch_backtrack(st, d_jobs, d_fin, nfin, choice, raw);
@@ -937,6 +944,11 @@ struct mib_encoder {
 extern "C" {
 
 void mib_force_no_dp_cache(int off) { __atomic_store_n(&g_no_dp_cache, off ? 1 : 0, __ATOMIC_RELAXED); }
+void mib_debug_dp_launches(uint64_t out[4]) {
+  unsigned long long v[4];
+  enc::dp_launch_counts(v);
+  for (int q = 0; q < 4; q++) out[q] = v[q];
+}
 
 void mib_encode_ws_free(void *p) {
   Workspace *ws = reinterpret_cast<Workspace *>(p);

@@ -533,6 +533,14 @@ def encode_batch(buffers, options=None, gpus=None):
     return res
 
 
+def debug_dp_launches():
+    """Diagnostic (tests): this process's launches of the parse's kernel so far, by pieces a
+    wave: {1: n, 2: n, 4: n, 8: n} (mib_debug_dp_launches)."""
+    out = (ctypes.c_uint64 * 4)()
+    _L().mib_debug_dp_launches(out)
+    return {1: out[0], 2: out[1], 4: out[2], 8: out[3]}
+
+
 def debug_match_records(buffers, options=None):
     """Diagnostic (tests): the records the encoder's bucket sort and candidate walk alone give
     a batch of buffers (mib_debug_match_records): per buffer a numpy uint32 array of shape

@@ -229,6 +229,10 @@ void mib_force_shards(int force);
  * finds a chosen distance in the ring), so a test can show what the candidates change; 0
  * restores them. */
 void mib_force_no_dp_cache(int off);
+/* Diagnostic (tests): how many launches of the parse's kernel this process has made so far with
+ * one, two, four and eight pieces (or segments) a wave: out[0..3].  A test reads it before and
+ * after a call to see which build of the parse the call took. */
+void mib_debug_dp_launches(uint64_t out[4]);
 /* Diagnostic (tests): the match finder's candidate walk alone.  The k host buffers are laid
  * out as one encode call lays them out and only that call's bucket sort and find_matches run
  * (no near scan, no dictionary passes, no history); `o` gives quality (depth), lgwin (window)
