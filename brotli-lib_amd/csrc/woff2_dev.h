@@ -1,0 +1,83 @@
+// What the WOFF2 host entry points (woff2_inv.hip, woff2_file.hip) share: a call's device
+// buffers, its per-kernel timer, and the reconstruct cores that work on device memory.
+#ifndef MIB_WOFF2_DEV_H_
+#define MIB_WOFF2_DEV_H_
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <utility>
+#include <vector>
+
+#include "common.h"
+
+extern "C" mib_ctx *mib_default_ctx(void);
+extern "C" void mib_default_lock(int on);
+extern "C" void *mib_ctx_stream_of(mib_ctx *c);
+extern "C" int mib_ctx_device_of(mib_ctx *c);
+extern "C" int mib_ctx_profiling(mib_ctx *c);
+extern "C" void mib_ctx_add_time(mib_ctx *c, const char *name, double ms);
+
+namespace mib {
+namespace woff2dev {
+
+struct Timer {   // per-kernel device time when the context profiles (mib_ctx_set_profiling)
+  mib_ctx *c;
+  hipStream_t s;
+  bool on;
+  std::vector<std::pair<const char *, std::pair<hipEvent_t, hipEvent_t>>> ev;
+  void start(const char *name) {
+    if (!on) return;
+    hipEvent_t a, b;
+    hipEventCreate(&a);
+    hipEventCreate(&b);
+    hipEventRecord(a, s);
+    ev.push_back({name, {a, b}});
+  }
+  void stop() {
+    if (on) hipEventRecord(ev.back().second.second, s);
+  }
+  void collect(bool ok) {
+    for (auto &e : ev) {
+      float ms = 0;
+      if (ok && hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess)
+        mib_ctx_add_time(c, e.first, ms);
+      hipEventDestroy(e.second.first);
+      hipEventDestroy(e.second.second);
+    }
+    ev.clear();
+  }
+};
+
+// The call's device buffers, freed together.  Each has 16 bytes of slack behind it: what a
+// 16-byte vector read of its last bytes may touch (load16.h).
+struct DevMem {
+  std::vector<void *> p;
+  template <class T>
+  T *take(size_t count) {
+    void *q = nullptr;
+    if (hipMalloc(&q, sizeof(T) * (count ? count : 1) + 16) != hipSuccess) return nullptr;
+    p.push_back(q);
+    return (T *)q;
+  }
+  ~DevMem() {
+    for (void *q : p) hipFree(q);
+  }
+};
+
+// The reconstruct entry points' work between upload and download.  The caller holds the
+// default context's lock, has set its device, and owns `m` (the results live in it) and `tm`.
+// Return codes as the entry points'; on 0 the stream has been synchronised.
+//   glyf: the transformed table's n bytes at d_t, `hdr` a host copy of its first 36
+//         (woff2_inv.h parse_header has to have accepted hdr, n).  loca follows glyf in memory.
+int reconstruct_glyf_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *hdr, const uint8_t *d_t, size_t n,
+                            uint8_t **d_glyf, size_t *glyf_b, uint8_t **d_loca, size_t *loca_b);
+//   hmtx: the transformed table's n >= 1 bytes at d_t; its flags and size are checked on the
+//         device.  The caller has checked num_glyphs, num_hmetrics and loca_n (hmtx_shape_ok).
+int reconstruct_hmtx_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *d_t, size_t n, const uint8_t *d_glyf,
+                            size_t glyf_n, const uint8_t *d_loca, uint32_t long_loca, uint32_t num_glyphs,
+                            uint32_t num_hmetrics, uint8_t **d_out, size_t *out_b);
+
+}  // namespace woff2dev
+}  // namespace mib
+#endif

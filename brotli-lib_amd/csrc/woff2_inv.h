@@ -507,17 +507,23 @@ MIB_HD inline bool hmtx_glyph(const uint8_t *t, const uint8_t *glyf, uint32_t gl
   return true;
 }
 // argument checks of mib_woff2_reconstruct_hmtx; *long_loca from the loca table's size
-inline bool hmtx_args_ok(const uint8_t *t, size_t n, size_t glyf_n, size_t loca_n, uint32_t ng, uint32_t nhm,
-                         uint32_t *long_loca) {
-  if (!t || n < 1 || ng == 0 || ng > 65535 || nhm == 0 || nhm > ng || glyf_n > 0xFFFFFFFFull) return false;
-  const uint32_t flags = t[0];
+// in two halves: what the table's first byte decides (reserved bits, a flag set, the size the
+// flags imply -- the device checks this where the table never visits the host), and the rest
+MIB_HD inline bool hmtx_flags_ok(uint32_t flags, uint64_t n, uint32_t ng, uint32_t nhm) {
   if ((flags & 0xFC) || !(flags & 3)) return false;
   const uint64_t want = 1 + 2ull * nhm + ((flags & 1) ? 0 : 2ull * nhm) + ((flags & 2) ? 0 : 2ull * (ng - nhm));
-  if (n != want) return false;
+  return n == want;
+}
+inline bool hmtx_shape_ok(size_t n, size_t glyf_n, size_t loca_n, uint32_t ng, uint32_t nhm, uint32_t *long_loca) {
+  if (n < 1 || ng == 0 || ng > 65535 || nhm == 0 || nhm > ng || glyf_n > 0xFFFFFFFFull) return false;
   if (loca_n == 4 * ((size_t)ng + 1)) *long_loca = 1;
   else if (loca_n == 2 * ((size_t)ng + 1)) *long_loca = 0;
   else return false;
   return true;
+}
+inline bool hmtx_args_ok(const uint8_t *t, size_t n, size_t glyf_n, size_t loca_n, uint32_t ng, uint32_t nhm,
+                         uint32_t *long_loca) {
+  return t && hmtx_shape_ok(n, glyf_n, loca_n, ng, nhm, long_loca) && hmtx_flags_ok(t[0], n, ng, nhm);
 }
 inline int host_reconstruct_hmtx(const uint8_t *t, size_t n, const uint8_t *glyf, size_t glyf_n, const uint8_t *loca,
                                  size_t loca_n, uint32_t ng, uint32_t nhm, std::vector<uint8_t> *out) {

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.h"
+#include "woff2_dev.h"
 #include "woff2_inv.h"
 
 namespace mib {
@@ -337,10 +338,15 @@ __global__ void inv_loca_kernel(uint32_t ng, uint32_t long_loca, const uint32_t 
   if (i <= ng) put_loca(loca, long_loca, i, off[i]);
 }
 
-__global__ void inv_hmtx_kernel(const uint8_t *t, const uint8_t *glyf, uint32_t glyf_n, const uint8_t *loca,
+// (n >= 1: the table's flags are its first byte)
+__global__ void inv_hmtx_kernel(const uint8_t *t, uint64_t n, const uint8_t *glyf, uint32_t glyf_n, const uint8_t *loca,
                                 uint32_t long_loca, uint32_t ng, uint32_t nhm, uint8_t *out, int *bad) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ng) return;
+  if (!hmtx_flags_ok(t[0], n, ng, nhm)) {   // nothing behind the flags is read then
+    atomicOr(bad, 1);
+    return;
+  }
   if (!hmtx_glyph(t, glyf, glyf_n, loca, long_loca, ng, nhm, g, out)) atomicOr(bad, 1);
 }
 
@@ -348,57 +354,10 @@ __global__ void inv_hmtx_kernel(const uint8_t *t, const uint8_t *glyf, uint32_t 
 }  // namespace mib
 
 using namespace mib::woff2inv;
-
-extern "C" mib_ctx *mib_default_ctx(void);
-extern "C" void mib_default_lock(int on);
-extern "C" void *mib_ctx_stream_of(mib_ctx *c);
-extern "C" int mib_ctx_device_of(mib_ctx *c);
-extern "C" int mib_ctx_profiling(mib_ctx *c);
-extern "C" void mib_ctx_add_time(mib_ctx *c, const char *name, double ms);
+using mib::woff2dev::DevMem;
+using mib::woff2dev::Timer;
 
 namespace {
-
-struct Timer {   // per-kernel device time when the context profiles (mib_ctx_set_profiling)
-  mib_ctx *c;
-  hipStream_t s;
-  bool on;
-  std::vector<std::pair<const char *, std::pair<hipEvent_t, hipEvent_t>>> ev;
-  void start(const char *name) {
-    if (!on) return;
-    hipEvent_t a, b;
-    hipEventCreate(&a);
-    hipEventCreate(&b);
-    hipEventRecord(a, s);
-    ev.push_back({name, {a, b}});
-  }
-  void stop() {
-    if (on) hipEventRecord(ev.back().second.second, s);
-  }
-  void collect(bool ok) {
-    for (auto &e : ev) {
-      float ms = 0;
-      if (ok && hipEventElapsedTime(&ms, e.second.first, e.second.second) == hipSuccess)
-        mib_ctx_add_time(c, e.first, ms);
-      hipEventDestroy(e.second.first);
-      hipEventDestroy(e.second.second);
-    }
-    ev.clear();
-  }
-};
-
-struct DevMem {   // the call's device buffers, freed together
-  std::vector<void *> p;
-  template <class T>
-  T *take(size_t count) {
-    void *q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (count ? count : 1) + 16) != hipSuccess) return nullptr;
-    p.push_back(q);
-    return (T *)q;
-  }
-  ~DevMem() {
-    for (void *q : p) hipFree(q);
-  }
-};
 
 bool scan(DevMem &m, const uint32_t *in, uint32_t *out, size_t count, hipStream_t st) {
   size_t tmp_b = 0;
@@ -417,6 +376,106 @@ extern "C" void mib_woff2_inv_last_steps(uint32_t out[2]) {
   out[1] = g_last_steps[1];
 }
 
+int mib::woff2dev::reconstruct_glyf_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *hdr, const uint8_t *d_t,
+                                           size_t n, uint8_t **d_glyf, size_t *glyf_b_out, uint8_t **d_loca,
+                                           size_t *loca_b_out) {
+  View hv, v;
+  if (!parse_header(hdr, n, hdr, &hv) || !parse_header(hdr, n, d_t, &v)) return MIB_E_INVALID_ARG;
+  const uint32_t ng = hv.num_glyphs;
+  const size_t g1 = (size_t)ng + 1;
+  const uint32_t np_cap = hv.n[kNPoints], comp_cap = hv.n[kComposite] / 6 + 1;
+  uint32_t *d_counts = m.take<uint32_t>(kCounts * g1), *d_counts_x = m.take<uint32_t>(kCounts * g1);
+  uint32_t *d_pts = m.take<uint32_t>((size_t)np_cap + 1), *d_pts_x = m.take<uint32_t>((size_t)np_cap + 1);
+  uint32_t *d_pos = m.take<uint32_t>((size_t)np_cap + 1);
+  uint32_t *d_coff = m.take<uint32_t>((size_t)comp_cap + 1), *d_chi = m.take<uint32_t>((size_t)comp_cap + 1);
+  uint32_t *d_cur = m.take<uint32_t>(kStreams * g1);
+  uint32_t *d_T = m.take<uint32_t>(g1), *d_h = m.take<uint32_t>(g1), *d_ilen = m.take<uint32_t>(g1);
+  uint32_t *d_sizes = m.take<uint32_t>(g1), *d_off = m.take<uint32_t>(g1);
+  uint32_t *d_steps = m.take<uint32_t>(2);
+  int *d_bad = m.take<int>(1);
+  if (!d_counts || !d_counts_x || !d_pts || !d_pts_x || !d_pos || !d_coff || !d_chi || !d_cur || !d_T || !d_h || !d_ilen ||
+      !d_sizes || !d_off || !d_steps || !d_bad)
+    return MIB_E_OUT_OF_MEMORY;
+  CurArrays cur;
+  for (int s = 0; s < kStreams; s++) cur.c[s] = d_cur + (size_t)s * g1;
+  hipMemsetAsync(d_bad, 0, 4, st);
+  hipMemsetAsync(d_steps, 0, 8, st);
+  hipMemsetAsync(d_pts, 0, 4 * ((size_t)np_cap + 1), st);
+  hipMemsetAsync(d_pos, 0, 4 * ((size_t)np_cap + 1), st);
+  hipMemsetAsync(d_coff, 0, 4 * ((size_t)comp_cap + 1), st);
+  hipMemsetAsync(d_chi, 0, 4 * ((size_t)comp_cap + 1), st);
+  hipMemsetAsync(d_cur, 0, 4 * kStreams * g1, st);
+  hipMemsetAsync(d_ilen, 0, 4 * g1, st);
+  const dim3 grid1((uint32_t)((g1 + 255) / 256)), block(256);
+  bool ok = true;
+  tm.start("w2inv_count");
+  hipLaunchKernelGGL(inv_count_kernel, grid1, block, 0, st, v, d_counts, d_bad);
+  tm.stop();
+  tm.start("w2inv_scan_counts");
+  ok = ok && scan(m, d_counts, d_counts_x, kCounts * g1, st);
+  tm.stop();
+  tm.start("w2inv_npoints");
+  hipLaunchKernelGGL(inv_npoints_kernel, dim3(1), dim3(kWave), 0, st, v, d_counts_x + (size_t)kCntContours * g1, d_pts,
+                     d_pos, d_steps, d_bad);
+  tm.stop();
+  tm.start("w2inv_scan_points");
+  ok = ok && scan(m, d_pts, d_pts_x, (size_t)np_cap + 1, st);
+  tm.stop();
+  tm.start("w2inv_comp");
+  hipLaunchKernelGGL(inv_comp_kernel, dim3(1), dim3(kWave), 0, st, v, d_counts_x + (size_t)kCntComp * g1, comp_cap, d_coff,
+                     d_chi, d_bad);
+  tm.stop();
+  tm.start("w2inv_measure");
+  hipLaunchKernelGGL(inv_measure_kernel, grid1, block, 0, st, v, d_counts_x, d_pts_x, d_pos, d_coff, d_chi, comp_cap, cur,
+                     d_T, d_h);
+  tm.stop();
+  tm.start("w2inv_chain");
+  hipLaunchKernelGGL(inv_chain_kernel, dim3(1), dim3(kWave), 0, st, v, d_T, d_h, cur.c[kGlyph], d_ilen, d_steps, d_bad);
+  tm.stop();
+  tm.start("w2inv_scan_instr");
+  ok = ok && scan(m, d_ilen, cur.c[kInstr], g1, st);
+  tm.stop();
+  tm.start("w2inv_size");
+  hipLaunchKernelGGL(inv_size_kernel, grid1, block, 0, st, v, cur, d_sizes, d_bad);
+  tm.stop();
+  tm.start("w2inv_scan_sizes");
+  ok = ok && scan(m, d_sizes, d_off, g1, st);
+  tm.stop();
+  if (!ok) {
+    hipStreamSynchronize(st);
+    return MIB_E_OUT_OF_MEMORY;
+  }
+  int bad = 0;
+  uint32_t total = 0, steps[2] = {0, 0};
+  Cursors end;
+  end.c[kNContour] = 0;
+  hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(&total, d_off + ng, 4, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(steps, d_steps, 8, hipMemcpyDeviceToHost, st);
+  for (int s = kNPoints; s < kStreams; s++) hipMemcpyAsync(&end.c[s], cur.c[s] + ng, 4, hipMemcpyDeviceToHost, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return MIB_E_NO_DEVICE;
+  g_last_steps[0] = steps[0];
+  g_last_steps[1] = steps[1];
+  // a malformed glyph; streams not used up exactly; offsets that loca format 0 cannot hold
+  if (bad || !totals_ok(hv, end, total)) return MIB_E_INVALID_ARG;
+  // the size comes from the sizing pass alone (every glyph empty: one zero byte, as fontTools)
+  const size_t glyf_b = total ? total : 1, loca_b = g1 * (hv.long_loca ? 4 : 2);
+  uint8_t *d_out = m.take<uint8_t>(glyf_b + loca_b);
+  if (!d_out) return MIB_E_OUT_OF_MEMORY;
+  if (!total) hipMemsetAsync(d_out, 0, 1, st);
+  tm.start("w2inv_write");
+  hipLaunchKernelGGL(inv_write_kernel, grid1, block, 0, st, v, cur, d_off, d_out);
+  tm.stop();
+  tm.start("w2inv_loca");
+  hipLaunchKernelGGL(inv_loca_kernel, grid1, block, 0, st, ng, hv.long_loca, d_off, d_out + glyf_b);
+  tm.stop();
+  *d_glyf = d_out;
+  *glyf_b_out = glyf_b;
+  *d_loca = d_out + glyf_b;
+  *loca_b_out = loca_b;
+  return 0;
+}
+
 extern "C" int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_buf *glyf, mib_buf *loca) {
   if (!glyf || !loca) return MIB_E_INVALID_ARG;
   glyf->data = loca->data = nullptr;
@@ -424,7 +483,6 @@ extern "C" int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_bu
   if (!tglyf) return MIB_E_INVALID_ARG;
   View hv;
   if (!parse_header(tglyf, n, tglyf, &hv)) return MIB_E_INVALID_ARG;
-  const uint32_t ng = hv.num_glyphs;
   mib_default_lock(1);
   mib_ctx *c = mib_default_ctx();
   if (!c) {
@@ -439,111 +497,14 @@ extern "C" int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_bu
   {
     DevMem m;
     do {
-      const size_t g1 = (size_t)ng + 1;
-      const uint32_t np_cap = hv.n[kNPoints], comp_cap = hv.n[kComposite] / 6 + 1;
-      uint8_t *d_t = m.take<uint8_t>(n);
-      uint32_t *d_counts = m.take<uint32_t>(kCounts * g1), *d_counts_x = m.take<uint32_t>(kCounts * g1);
-      uint32_t *d_pts = m.take<uint32_t>((size_t)np_cap + 1), *d_pts_x = m.take<uint32_t>((size_t)np_cap + 1);
-      uint32_t *d_pos = m.take<uint32_t>((size_t)np_cap + 1);
-      uint32_t *d_coff = m.take<uint32_t>((size_t)comp_cap + 1), *d_chi = m.take<uint32_t>((size_t)comp_cap + 1);
-      uint32_t *d_cur = m.take<uint32_t>(kStreams * g1);
-      uint32_t *d_T = m.take<uint32_t>(g1), *d_h = m.take<uint32_t>(g1), *d_ilen = m.take<uint32_t>(g1);
-      uint32_t *d_sizes = m.take<uint32_t>(g1), *d_off = m.take<uint32_t>(g1);
-      uint32_t *d_steps = m.take<uint32_t>(2);
-      int *d_bad = m.take<int>(1);
-      if (!d_t || !d_counts || !d_counts_x || !d_pts || !d_pts_x || !d_pos || !d_coff || !d_chi || !d_cur || !d_T ||
-          !d_h || !d_ilen || !d_sizes || !d_off || !d_steps || !d_bad) {
+      uint8_t *d_t = m.take<uint8_t>(n), *d_glyf = nullptr, *d_loca = nullptr;
+      size_t glyf_b = 0, loca_b = 0;
+      if (!d_t) {
         rc = MIB_E_OUT_OF_MEMORY;
         break;
       }
-      View v;
-      parse_header(tglyf, n, d_t, &v);
-      CurArrays cur;
-      for (int s = 0; s < kStreams; s++) cur.c[s] = d_cur + (size_t)s * g1;
       hipMemcpyAsync(d_t, tglyf, n, hipMemcpyHostToDevice, st);
-      hipMemsetAsync(d_bad, 0, 4, st);
-      hipMemsetAsync(d_steps, 0, 8, st);
-      hipMemsetAsync(d_pts, 0, 4 * ((size_t)np_cap + 1), st);
-      hipMemsetAsync(d_pos, 0, 4 * ((size_t)np_cap + 1), st);
-      hipMemsetAsync(d_coff, 0, 4 * ((size_t)comp_cap + 1), st);
-      hipMemsetAsync(d_chi, 0, 4 * ((size_t)comp_cap + 1), st);
-      hipMemsetAsync(d_cur, 0, 4 * kStreams * g1, st);
-      hipMemsetAsync(d_ilen, 0, 4 * g1, st);
-      const dim3 grid1((uint32_t)((g1 + 255) / 256)), block(256);
-      bool ok = true;
-      tm.start("w2inv_count");
-      hipLaunchKernelGGL(inv_count_kernel, grid1, block, 0, st, v, d_counts, d_bad);
-      tm.stop();
-      tm.start("w2inv_scan_counts");
-      ok = ok && scan(m, d_counts, d_counts_x, kCounts * g1, st);
-      tm.stop();
-      tm.start("w2inv_npoints");
-      hipLaunchKernelGGL(inv_npoints_kernel, dim3(1), dim3(kWave), 0, st, v,
-                         d_counts_x + (size_t)kCntContours * g1, d_pts, d_pos, d_steps, d_bad);
-      tm.stop();
-      tm.start("w2inv_scan_points");
-      ok = ok && scan(m, d_pts, d_pts_x, (size_t)np_cap + 1, st);
-      tm.stop();
-      tm.start("w2inv_comp");
-      hipLaunchKernelGGL(inv_comp_kernel, dim3(1), dim3(kWave), 0, st, v, d_counts_x + (size_t)kCntComp * g1, comp_cap,
-                         d_coff, d_chi, d_bad);
-      tm.stop();
-      tm.start("w2inv_measure");
-      hipLaunchKernelGGL(inv_measure_kernel, grid1, block, 0, st, v, d_counts_x, d_pts_x, d_pos, d_coff, d_chi,
-                         comp_cap, cur, d_T, d_h);
-      tm.stop();
-      tm.start("w2inv_chain");
-      hipLaunchKernelGGL(inv_chain_kernel, dim3(1), dim3(kWave), 0, st, v, d_T, d_h, cur.c[kGlyph], d_ilen, d_steps,
-                         d_bad);
-      tm.stop();
-      tm.start("w2inv_scan_instr");
-      ok = ok && scan(m, d_ilen, cur.c[kInstr], g1, st);
-      tm.stop();
-      tm.start("w2inv_size");
-      hipLaunchKernelGGL(inv_size_kernel, grid1, block, 0, st, v, cur, d_sizes, d_bad);
-      tm.stop();
-      tm.start("w2inv_scan_sizes");
-      ok = ok && scan(m, d_sizes, d_off, g1, st);
-      tm.stop();
-      if (!ok) {
-        hipStreamSynchronize(st);
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      int bad = 0;
-      uint32_t total = 0, steps[2] = {0, 0};
-      Cursors end;
-      end.c[kNContour] = 0;
-      hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
-      hipMemcpyAsync(&total, d_off + ng, 4, hipMemcpyDeviceToHost, st);
-      hipMemcpyAsync(steps, d_steps, 8, hipMemcpyDeviceToHost, st);
-      for (int s = kNPoints; s < kStreams; s++)
-        hipMemcpyAsync(&end.c[s], cur.c[s] + ng, 4, hipMemcpyDeviceToHost, st);
-      if (hipStreamSynchronize(st) != hipSuccess) {
-        rc = MIB_E_NO_DEVICE;
-        break;
-      }
-      g_last_steps[0] = steps[0];
-      g_last_steps[1] = steps[1];
-      // a malformed glyph; streams not used up exactly; offsets that loca format 0 cannot hold
-      if (bad || !totals_ok(hv, end, total)) {
-        rc = MIB_E_INVALID_ARG;
-        break;
-      }
-      // the size comes from the sizing pass alone (every glyph empty: one zero byte, as fontTools)
-      const size_t glyf_b = total ? total : 1, loca_b = g1 * (hv.long_loca ? 4 : 2);
-      uint8_t *d_out = m.take<uint8_t>(glyf_b + loca_b);
-      if (!d_out) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      if (!total) hipMemsetAsync(d_out, 0, 1, st);
-      tm.start("w2inv_write");
-      hipLaunchKernelGGL(inv_write_kernel, grid1, block, 0, st, v, cur, d_off, d_out);
-      tm.stop();
-      tm.start("w2inv_loca");
-      hipLaunchKernelGGL(inv_loca_kernel, grid1, block, 0, st, ng, hv.long_loca, d_off, d_out + glyf_b);
-      tm.stop();
+      if ((rc = mib::woff2dev::reconstruct_glyf_device(st, tm, m, tglyf, d_t, n, &d_glyf, &glyf_b, &d_loca, &loca_b))) break;
       glyf->data = mib_buf_alloc(glyf_b);
       loca->data = mib_buf_alloc(loca_b);
       if (!glyf->data || !loca->data) {
@@ -553,8 +514,8 @@ extern "C" int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_bu
       }
       glyf->size = glyf_b;
       loca->size = loca_b;
-      hipMemcpyAsync(glyf->data, d_out, glyf_b, hipMemcpyDeviceToHost, st);
-      hipMemcpyAsync(loca->data, d_out + glyf_b, loca_b, hipMemcpyDeviceToHost, st);
+      hipMemcpyAsync(glyf->data, d_glyf, glyf_b, hipMemcpyDeviceToHost, st);
+      hipMemcpyAsync(loca->data, d_loca, loca_b, hipMemcpyDeviceToHost, st);
       if (hipStreamSynchronize(st) != hipSuccess) {
         rc = MIB_E_NO_DEVICE;
         break;
@@ -573,6 +534,28 @@ extern "C" int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_bu
   return rc;
 }
 
+int mib::woff2dev::reconstruct_hmtx_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *d_t, size_t n,
+                                           const uint8_t *d_glyf, size_t glyf_n, const uint8_t *d_loca, uint32_t long_loca,
+                                           uint32_t ng, uint32_t nhm, uint8_t **d_out_p, size_t *out_b) {
+  const size_t total = 4 * (size_t)nhm + 2 * (size_t)(ng - nhm);
+  uint8_t *d_out = m.take<uint8_t>(total);
+  int *d_bad = m.take<int>(1);
+  if (!d_out || !d_bad) return MIB_E_OUT_OF_MEMORY;
+  hipMemsetAsync(d_bad, 0, 4, st);
+  tm.start("w2inv_hmtx");
+  hipLaunchKernelGGL(inv_hmtx_kernel, dim3((ng + 255) / 256), dim3(256), 0, st, d_t, (uint64_t)n, d_glyf, (uint32_t)glyf_n,
+                     d_loca, long_loca, ng, nhm, d_out, d_bad);
+  tm.stop();
+  int bad = 0;
+  hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return MIB_E_NO_DEVICE;
+  // flags that do not fit the size; a loca entry that does not fit the glyf table
+  if (bad) return MIB_E_INVALID_ARG;
+  *d_out_p = d_out;
+  *out_b = total;
+  return 0;
+}
+
 extern "C" int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const uint8_t *glyf, size_t glyf_n,
                                           const uint8_t *loca, size_t loca_n, uint32_t num_glyphs,
                                           uint32_t num_hmetrics, mib_buf *out) {
@@ -583,7 +566,6 @@ extern "C" int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const 
   if (!loca || (!glyf && glyf_n) ||
       !hmtx_args_ok(thmtx, n, glyf_n, loca_n, num_glyphs, num_hmetrics, &long_loca))
     return MIB_E_INVALID_ARG;
-  const uint32_t ng = num_glyphs, nhm = num_hmetrics;
   mib_default_lock(1);
   mib_ctx *c = mib_default_ctx();
   if (!c) {
@@ -598,26 +580,22 @@ extern "C" int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const 
   {
     DevMem m;
     do {
-      const size_t total = 4 * (size_t)nhm + 2 * (size_t)(ng - nhm);
-      uint8_t *d_in = m.take<uint8_t>(n + glyf_n + loca_n), *d_out = m.take<uint8_t>(total);
-      int *d_bad = m.take<int>(1);
-      if (!d_in || !d_out || !d_bad) {
+      uint8_t *d_in = m.take<uint8_t>(n + glyf_n + loca_n), *d_out = nullptr;
+      size_t total = 0;
+      if (!d_in) {
         rc = MIB_E_OUT_OF_MEMORY;
         break;
       }
       hipMemcpyAsync(d_in, thmtx, n, hipMemcpyHostToDevice, st);
       if (glyf_n) hipMemcpyAsync(d_in + n, glyf, glyf_n, hipMemcpyHostToDevice, st);
       hipMemcpyAsync(d_in + n + glyf_n, loca, loca_n, hipMemcpyHostToDevice, st);
-      hipMemsetAsync(d_bad, 0, 4, st);
-      tm.start("w2inv_hmtx");
-      hipLaunchKernelGGL(inv_hmtx_kernel, dim3((ng + 255) / 256), dim3(256), 0, st, d_in, d_in + n, (uint32_t)glyf_n,
-                         d_in + n + glyf_n, long_loca, ng, nhm, d_out, d_bad);
-      tm.stop();
-      int bad = 0;
-      hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
+      if ((rc = mib::woff2dev::reconstruct_hmtx_device(st, tm, m, d_in, n, d_in + n, glyf_n, d_in + n + glyf_n, long_loca,
+                                                       num_glyphs, num_hmetrics, &d_out, &total))) {
+        timed = rc == MIB_E_INVALID_ARG;   // (the kernel ran)
+        break;
+      }
       out->data = mib_buf_alloc(total);
       if (!out->data) {
-        hipStreamSynchronize(st);
         rc = MIB_E_OUT_OF_MEMORY;
         break;
       }
@@ -628,7 +606,6 @@ extern "C" int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const 
         break;
       }
       timed = true;
-      if (bad) rc = MIB_E_INVALID_ARG;   // a loca entry that does not fit the glyf table
     } while (0);
     tm.collect(timed);
   }

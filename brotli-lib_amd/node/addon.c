@@ -607,6 +607,24 @@ static napi_value js_woff2(napi_env env, napi_callback_info info, int hmtx) {
 }
 static napi_value js_woff2_glyf(napi_env env, napi_callback_info info) { return js_woff2(env, info, 0); }
 static napi_value js_woff2_hmtx(napi_env env, napi_callback_info info) { return js_woff2(env, info, 1); }
+/* woff2File(data) -> Buffer: the sfnt a .woff2 file stands for, decoded, reconstructed and
+ * assembled on the GPU; a file that does not parse throws (MIB_E_INVALID_ARG, or the decoder's
+ * code for its Brotli stream) */
+static napi_value js_woff2_file(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  const uint8_t *p;
+  size_t n;
+  if (argc < 1 || get_bytes(env, argv[0], &p, &n)) {
+    napi_throw_type_error(env, NULL, "input must be a Uint8Array");
+    return NULL;
+  }
+  mib_buf b = {0, 0};
+  const int rc = mib_woff2_decode(p, n, &b);
+  if (rc) return throw_code(env, rc);
+  return take(env, &b);
+}
 /* woff2InvGlyf(data) -> [glyf, loca] (Buffers): the TrueType tables of a WOFF2-transformed glyf
  * table, computed on the GPU; a table that does not parse throws (MIB_E_INVALID_ARG) */
 static napi_value js_woff2_inv_glyf(napi_env env, napi_callback_info info) {
@@ -679,6 +697,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"woff2Hmtx", 0, js_woff2_hmtx, 0, 0, 0, napi_default, 0},
       {"woff2InvGlyf", 0, js_woff2_inv_glyf, 0, 0, 0, napi_default, 0},
       {"woff2InvHmtx", 0, js_woff2_inv_hmtx, 0, 0, 0, napi_default, 0},
+      {"woff2File", 0, js_woff2_file, 0, 0, 0, napi_default, 0},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

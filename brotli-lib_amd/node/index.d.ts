@@ -87,3 +87,5 @@ export declare function woff2TransformHmtx(ttf: Uint8Array): Uint8Array | null
 export declare function woff2ReconstructGlyf(data: Uint8Array): { glyf: Uint8Array, loca: Uint8Array }
 /** inverse of woff2TransformHmtx: the dropped side bearings are the glyphs' xMin in glyf / loca */
 export declare function woff2ReconstructHmtx(data: Uint8Array, glyf: Uint8Array, loca: Uint8Array, numGlyphs: number, numHMetrics: number): Uint8Array
+/** a .woff2 file (single font) -> the sfnt it stands for, decoded, reconstructed and assembled on the GPU (records sorted by tag, tables in the file's order, checksums computed); throws on a file that does not parse */
+export declare function woff2Decode(data: Uint8Array): Uint8Array

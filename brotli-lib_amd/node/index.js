@@ -170,10 +170,16 @@ function woff2ReconstructGlyf(data) {
 function woff2ReconstructHmtx(data, glyf, loca, numGlyphs, numHMetrics) {
   return toU8(native.woff2InvHmtx(data, glyf, loca, numGlyphs, numHMetrics))
 }
+// a whole .woff2 file (single font) -> its sfnt: Brotli decode, reconstruction and assembly
+// (records by tag, checksums, head's checkSumAdjustment) on the GPU; throws on a file that
+// does not parse
+function woff2Decode(data) {
+  return toU8(native.woff2File(data))
+}
 
 module.exports = {
   brotliEncode, BrotliEncoder, brotliDecode, BrotliDecoder, brotliDecodedSize, EncoderMode,
   brotliEncodeBatch, brotliEncodeBatchAsync, brotliDecodeBatchAsync,
   brotliDecoderUpdateBatch, brotliDecoderFinishBatch,
-  woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx,
+  woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx, woff2Decode,
 }

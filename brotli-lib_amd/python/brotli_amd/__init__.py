@@ -18,7 +18,8 @@ import os
 
 __all__ = ['brotliEncode', 'BrotliEncoder', 'brotliDecode', 'BrotliDecoder', 'brotliDecodedSize', 'EncoderMode', 'BrotliError',
            'encode_batch', 'decode_batch', 'encoder_update_batch', 'decoder_update_batch', 'decoder_finish_batch',
-           'decoder_update_batch_device', 'decoder_finish_batch_device', 'MORE_OUTPUT', 'DeviceContext', 'library_path']
+           'decoder_update_batch_device', 'decoder_finish_batch_device', 'MORE_OUTPUT', 'DeviceContext', 'library_path',
+           'woff2_decode']
 
 _PKG = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # BROTLI_AMD_LIB: an instrumented build of the same library (timing experiments only)
@@ -191,6 +192,11 @@ def _L():
         lib.mib_woff2_reconstruct_hmtx.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                                    ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                                    ctypes.POINTER(_Buf)]
+        if hasattr(lib, 'mib_woff2_decode'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_woff2_decode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
+            lib.mib_debug_sfnt_assemble.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                                    ctypes.POINTER(_Span), ctypes.c_char_p, ctypes.c_size_t,
+                                                    ctypes.POINTER(_Buf)]
         lib.mib_part_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         if hasattr(lib, 'mib_debug_match_records'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_debug_match_records.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
@@ -626,6 +632,42 @@ def woff2_reconstruct_hmtx(data, glyf, loca, num_glyphs, num_hmetrics):
     buf = _Buf()
     rc = _L().mib_woff2_reconstruct_hmtx(data, len(data), glyf, len(glyf), loca, len(loca), int(num_glyphs),
                                          int(num_hmetrics), ctypes.byref(buf))
+    if rc:
+        raise _err(rc)
+    return _take(buf)
+
+
+def woff2_decode(data):
+    """The sfnt a .woff2 file (W3C WOFF2, single font) stands for: the Brotli stream decoded, glyf,
+    loca and hmtx reconstructed and the font assembled on the GPU -- records sorted by tag, tables
+    in the file's order at 4-byte boundaries, checksums and head's checkSumAdjustment computed.
+    The file is untrusted: one that does not parse raises BrotliError (MIB_E_INVALID_ARG, or the
+    decoder's code for a corrupt Brotli stream)."""
+    data = _bytes(data)
+    buf = _Buf()
+    rc = _L().mib_woff2_decode(data, len(data), ctypes.byref(buf))
+    if rc:
+        raise _err(rc)
+    return _take(buf)
+
+
+def debug_sfnt_assemble(flavor, tables, misalign=None):
+    """Diagnostic (tests): woff2_decode's assembly kernels alone over [(tag, bytes)], tags of four
+    bytes; misalign[i] in 0..15 is the misalignment table i's bytes get in device memory (None:
+    packed back to back)."""
+    tables = [(bytes(tag), _bytes(data)) for tag, data in tables]
+    k = len(tables)
+    if any(len(tag) != 4 for tag, _ in tables) or (misalign is not None and len(misalign) != k):
+        raise _err(-101)   # MIB_E_INVALID_ARG
+    tags = (ctypes.c_uint32 * max(k, 1))(*[int.from_bytes(tag, 'big') for tag, _ in tables])
+    keep = [ctypes.create_string_buffer(data, len(data)) for _, data in tables]
+    spans = (_Span * max(k, 1))()
+    for i, b in enumerate(keep):
+        spans[i].data = ctypes.cast(b, ctypes.c_void_p).value
+        spans[i].size = len(tables[i][1])
+    mis = bytes(misalign) if misalign is not None else None
+    buf = _Buf()
+    rc = _L().mib_debug_sfnt_assemble(int(flavor) & 0xFFFFFFFF, tags, spans, mis, k, ctypes.byref(buf))
     if rc:
         raise _err(rc)
     return _take(buf)

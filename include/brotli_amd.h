@@ -302,6 +302,24 @@ int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_buf *glyf, mi
 int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const uint8_t *glyf, size_t glyf_n,
                                const uint8_t *loca, size_t loca_n, uint32_t num_glyphs,
                                uint32_t num_hmetrics, mib_buf *out);
+/* A .woff2 file (W3C WOFF2, single font) -> the sfnt it stands for.  The Brotli stream is decoded
+ * and glyf, loca and hmtx are reconstructed (as the two functions above do) on the device, where
+ * the sfnt is assembled as well: offset table, table records sorted by tag, then
+ * the tables in the order of the file's directory, each at a 4-byte boundary and zero-padded;
+ * table checksums computed, head's checkSumAdjustment set (the rest of head, flags bit 11
+ * included, as in the file).  The file is untrusted: MIB_E_INVALID_ARG for a header or directory
+ * that does not parse (a font collection, a repeated tag, an undefined transform version, a
+ * malformed UIntBase128, lengths above 256 MiB ...), a stream that does not decode to exactly the
+ * directory's total, and whatever the reconstruct functions reject; the decoder's own negative
+ * code for a corrupt Brotli stream.  Metadata and private blocks are ignored.  On any error
+ * sfnt is {NULL, 0}. */
+int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt);
+/* Diagnostic (tests): the assembly kernels alone.  k tables (tag, bytes) in host memory are laid
+ * out as mib_woff2_decode lays a font out; d_src_misalign[i] in 0..15 is the misalignment table
+ * i's bytes get in the device source buffer (NULL: packed back to back, as in a decompressed
+ * WOFF2 stream). */
+int mib_debug_sfnt_assemble(uint32_t flavor, const uint32_t *tags, const mib_span *tables,
+                            const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt);
 
 /* Part-parallel decoding (streams this encoder marked with a part index):
  * how many streams a context (NULL: the default one) decoded part-parallel, and how many of
