@@ -1061,8 +1061,12 @@ static int decode_parts(mib_ctx *c, const std::vector<PartStream> &ps, std::vect
   return 0;
 }
 
-int mib_ctx_decode(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offsets, size_t k, uint8_t *d_out,
-                   const uint64_t *out_offsets, int64_t *out_sizes, int *status, void *stream) {
+// mib_ctx_decode's body.  out_caps: stream i's capacity where its slot is longer than what it may
+// write (slots padded to a boundary); null: the capacity is the slot, out_offsets[i + 1] -
+// out_offsets[i].
+static int decode_streams(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offsets, size_t k, uint8_t *d_out,
+                          const uint64_t *out_offsets, const uint64_t *out_caps, int64_t *out_sizes, int *status,
+                          void *stream) {
   if (!c || (k && (!d_in || !in_offsets || !d_out || !out_offsets))) return MIB_E_INVALID_ARG;
   if (ensure_device(c->device) != 0) return MIB_E_NO_DEVICE;
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
@@ -1085,7 +1089,7 @@ int mib_ctx_decode(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offsets, 
     j.in = d_in + in_offsets[i];
     j.in_len = in_offsets[i + 1] - in_offsets[i];
     j.out = d_out + out_offsets[i];
-    j.out_cap = out_offsets[i + 1] - out_offsets[i];
+    j.out_cap = out_caps ? out_caps[i] : out_offsets[i + 1] - out_offsets[i];
     j.out_size = -1;
     j.max_ring_log = peek_window_bits(&heads[16 * i], (size_t)std::min<uint64_t>(j.in_len, 2));
   }
@@ -1133,6 +1137,20 @@ int mib_ctx_decode(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offsets, 
     if (jobs[i].status) worst = jobs[i].status;
   }
   return worst == MIB_E_NEED_SPACE ? MIB_E_NEED_SPACE : 0;
+}
+
+int mib_ctx_decode(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offsets, size_t k, uint8_t *d_out,
+                   const uint64_t *out_offsets, int64_t *out_sizes, int *status, void *stream) {
+  return decode_streams(c, d_in, in_offsets, k, d_out, out_offsets, nullptr, out_sizes, status, stream);
+}
+
+// Internal (woff2_file.hip's batch): mib_ctx_decode with stream i's output at d_out +
+// out_offsets[i] (k entries) and its capacity out_caps[i], whatever lies between the slots.
+int mib_ctx_decode_caps(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offsets, size_t k, uint8_t *d_out,
+                        const uint64_t *out_offsets, const uint64_t *out_caps, int64_t *out_sizes, int *status,
+                        void *stream) {
+  if (k && !out_caps) return MIB_E_INVALID_ARG;
+  return decode_streams(c, d_in, in_offsets, k, d_out, out_offsets, out_caps, out_sizes, status, stream);
 }
 
 // one host stream through the device (brotliDecode semantics of decode.ts:18-65)

@@ -66,17 +66,34 @@ struct DevMem {
 };
 
 // The reconstruct entry points' work between upload and download.  The caller holds the
-// default context's lock, has set its device, and owns `m` (the results live in it) and `tm`.
+// default context's lock, has set its device, and owns the DevMems and `tm`.
 // Return codes as the entry points'; on 0 the stream has been synchronised.
 //   glyf: the transformed table's n bytes at d_t, `hdr` a host copy of its first 36
 //         (woff2_inv.h parse_header has to have accepted hdr, n).  loca follows glyf in memory.
-int reconstruct_glyf_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *hdr, const uint8_t *d_t, size_t n,
-                            uint8_t **d_glyf, size_t *glyf_b, uint8_t **d_loca, size_t *loca_b);
+//         The results live in `keep`, everything else in `m`: once the stream has been
+//         synchronised after the call, `m` may go before the results are used (the two may be
+//         one DevMem).
+int reconstruct_glyf_device(hipStream_t st, Timer &tm, DevMem &m, DevMem &keep, const uint8_t *hdr, const uint8_t *d_t,
+                            size_t n, uint8_t **d_glyf, size_t *glyf_b, uint8_t **d_loca, size_t *loca_b);
 //   hmtx: the transformed table's n >= 1 bytes at d_t; its flags and size are checked on the
 //         device.  The caller has checked num_glyphs, num_hmetrics and loca_n (hmtx_shape_ok).
 int reconstruct_hmtx_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *d_t, size_t n, const uint8_t *d_glyf,
                             size_t glyf_n, const uint8_t *d_loca, uint32_t long_loca, uint32_t num_glyphs,
                             uint32_t num_hmetrics, uint8_t **d_out, size_t *out_b);
+
+// One font of the hmtx launch (blockIdx.y): what reconstruct_hmtx_device takes, all on the device;
+// out has 4 * nhm + 2 * (ng - nhm) bytes.
+struct HmtxFont {
+  const uint8_t *t;
+  uint64_t n;
+  const uint8_t *glyf, *loca;
+  uint8_t *out;
+  uint32_t glyf_n, long_loca, ng, nhm;
+};
+// One launch ("w2inv_hmtx") over k >= 1 fonts whose descriptors are at d_fonts; most_ng: the
+// largest ng among them.  d_bad[f] (zeroed by the caller) is raised for a font whose flags do not
+// fit its size or whose loca does not fit its glyf.  Nothing is synchronised.
+void launch_hmtx(hipStream_t st, Timer &tm, const HmtxFont *d_fonts, size_t k, uint32_t most_ng, int *d_bad);
 
 }  // namespace woff2dev
 }  // namespace mib

@@ -2,22 +2,31 @@
 // The container is parsed on the host (woff2_file.h: the plan); the Brotli stream is decoded on
 // the device into one buffer; glyf, loca and hmtx are reconstructed from it in device memory
 // (woff2_inv.hip's cores); then two kernels lay the sfnt out:
-//   sfnt_assemble_kernel   every table in one launch (blockIdx.y: the table, its tiles over
-//                          blockIdx.x): copied to its place over the output's 16-byte granules,
+//   sfnt_assemble_kernel   every table in one launch (blockIdx.x: the table, its tiles over
+//                          blockIdx.y): copied to its place over the output's 16-byte granules,
 //                          zero-padded to 4 bytes, head's checkSumAdjustment cleared, and summed
 //                          as big-endian words while the bytes are in registers
-//   sfnt_directory_kernel  one wave: offset table, the records in tag order with the sums as
-//                          their checksums, the file's sum, head's checkSumAdjustment
+//   sfnt_directory_kernel  one wave a font: offset table, the records in tag order with the sums
+//                          as their checksums, the file's sum, head's checkSumAdjustment
 // Between the upload of the file's compressed bytes and the download of the sfnt only the
 // 36-byte transformed-glyf header, hhea's numberOfHMetrics and the reconstruct cores' totals and
 // flags visit the host.  woff2_file.h's host_assemble states the same result serially.
+//
+// mib_woff2_decode_batch works k files in shared launches (DESIGN.md 4c "A batch of files";
+// woff2_batch.h decides where the bytes go): per group of files one upload, one decode call over
+// every stream, one w2file_peek launch and read-back for the headers, the glyf reconstruct per
+// font, one hmtx launch, one launch of each assembly kernel over every font, and one
+// synchronisation for the downloads.  Each decode call starts the context's kernel times afresh:
+// after a call of more than one group the times reported are the last group's.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include <chrono>
 #include <vector>
 
 #include "common.h"
 #include "load16.h"
+#include "woff2_batch.h"
 #include "woff2_dev.h"
 #include "woff2_file.h"
 
@@ -25,22 +34,13 @@ namespace mib {
 namespace woff2file {
 
 constexpr int kWave = 64;
-constexpr int kAsmThreads = 256;
-constexpr uint64_t kAsmTile = (uint64_t)kAsmThreads * 16;
 constexpr uint32_t kAsmSpread = 256;   // blocks per table at most (each walks its tiles)
-constexpr uint32_t kNoZero = 0xFFFFFFFFu;
+constexpr uint32_t kPeekBytes = 40;    // a font's row of the peek: 36 + 2, padded
 
-// One table of the launch.  dst_off is a multiple of 4; src has any alignment and 16 readable
-// bytes of slack behind its allocation's last byte (load16.h).
-struct AsmDesc {
-  const uint8_t *src;
-  uint32_t dst_off, len;
-  uint32_t zero_at;   // head with its checkSumAdjustment: 8 (bytes 8..11 are stored as zero); else kNoZero
-  uint32_t pad;
-};
-// One record of the directory, in tag order.
-struct DirRec {
-  uint32_t tag, table, dst_off, len;
+// One font of the peek: the transformed glyf table's first 36 bytes and hhea's bytes 34..35
+// (null: not wanted; the row's bytes are then zero).
+struct PeekFont {
+  const uint8_t *glyf, *hhea34;
 };
 
 __device__ __forceinline__ uint32_t be_word(uint32_t w) { return __builtin_bswap32(w); }
@@ -58,14 +58,16 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
 // table's words: each thread sums its granule's, a wave adds its lanes' sums with cross-lane
 // adds and one lane adds the wave's into the table's sum.  The sum wraps, so the order of the
 // adds does not matter.
+// blockIdx.x: the table, of every font of the launch (a launch may hold more tables than the
+// 65,535 of the other grid dimensions); blockIdx.y: its share of the table's tiles.
 __global__ __launch_bounds__(kAsmThreads) void sfnt_assemble_kernel(const AsmDesc *descs, uint8_t *out, uint32_t *sums) {
-  const AsmDesc d = descs[blockIdx.y];
+  const AsmDesc d = descs[blockIdx.x];
   const uint32_t padded = (d.len + 3) & ~3u;   // (len <= 2^32 - 4: woff2_file.h layout)
-  const uint32_t mis = d.dst_off & 15;
+  const uint32_t mis = d.dst_off & 15;         // (the font's base is a multiple of 16)
   const uint64_t tiles = padded ? ((uint64_t)padded + mis + kAsmTile - 1) / kAsmTile : 0;
-  uint8_t *dst = out + d.dst_off;
+  uint8_t *dst = out + d.out_base + d.dst_off;
   uint32_t acc = 0;
-  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+  for (uint64_t t = blockIdx.y; t < tiles; t += gridDim.y) {
     const int64_t lo = (int64_t)(16 * (t * kAsmThreads + threadIdx.x)) - (int64_t)mis;   // the granule's first byte in the table
     if (lo >= (int64_t)padded) continue;
     if (lo >= 0 && (uint64_t)lo + 16 <= d.len) {
@@ -97,26 +99,29 @@ __global__ __launch_bounds__(kAsmThreads) void sfnt_assemble_kernel(const AsmDes
     }
   }
   acc = wave_sum(acc);
-  if ((threadIdx.x & (kWave - 1)) == 0 && acc) atomicAdd(&sums[blockIdx.y], acc);
+  if ((threadIdx.x & (kWave - 1)) == 0 && acc) atomicAdd(&sums[d.sum], acc);
 }
 
-// One wave.  The offset table and the records (their place, 12 + 16 r, is a multiple of 4: four
-// word stores each); every lane sums the words it writes and its records' table sums, the
-// wave's total is the file's sum, and head's checkSumAdjustment follows from it.
-__global__ __launch_bounds__(kWave) void sfnt_directory_kernel(uint32_t flavor, uint32_t num, uint32_t range, uint32_t selector,
-                                                              uint32_t shift, const DirRec *recs, const uint32_t *sums,
-                                                              uint32_t adjust_at, uint8_t *out) {
+// One wave per font (blockIdx.x).  The offset table and the records (their place, 12 + 16 r, is a
+// multiple of 4: four word stores each); every lane sums the words it writes and its records'
+// table sums, the wave's total is the file's sum, and head's checkSumAdjustment follows from it.
+__global__ __launch_bounds__(kWave) void sfnt_directory_kernel(const DirFont *fonts, const DirRec *all_recs,
+                                                              const uint32_t *all_sums, uint8_t *all_out) {
+  const DirFont f = fonts[blockIdx.x];
+  const DirRec *recs = all_recs + f.first_rec;
+  const uint32_t *sums = all_sums + f.first_sum;
+  uint8_t *out = all_out + f.out_base;
   const int lane = threadIdx.x;
   uint32_t *o = reinterpret_cast<uint32_t *>(out);
   uint32_t acc = 0;
   if (lane == 0) {
-    const uint32_t w0 = flavor, w1 = (num << 16) | range, w2 = (selector << 16) | shift;
+    const uint32_t w0 = f.flavor, w1 = (f.num << 16) | f.range, w2 = (f.selector << 16) | f.shift;
     o[0] = be_word(w0);
     o[1] = be_word(w1);
     o[2] = be_word(w2);
     acc = w0 + w1 + w2;
   }
-  for (uint32_t r = lane; r < num; r += kWave) {
+  for (uint32_t r = lane; r < f.num; r += kWave) {
     const DirRec rec = recs[r];
     const uint32_t cs = sums[rec.table];
     uint32_t *p = o + 3 + 4 * (size_t)r;
@@ -127,7 +132,19 @@ __global__ __launch_bounds__(kWave) void sfnt_directory_kernel(uint32_t flavor, 
     acc += rec.tag + cs + rec.dst_off + rec.len + cs;   // the record's words, and the table's own
   }
   acc = wave_sum(acc);
-  if (lane == 0 && adjust_at != kNoZero) *reinterpret_cast<uint32_t *>(out + adjust_at) = be_word(kHeadMagic - acc);
+  if (lane == 0 && f.adjust_at != kNoZero) *reinterpret_cast<uint32_t *>(out + f.adjust_at) = be_word(kHeadMagic - acc);
+}
+
+// A thread per font, in the shape of the decoder's peek_heads_kernel: what the host needs of every
+// font's decoded stream before it can size the reconstructed tables, in one read-back.
+__global__ void w2file_peek_kernel(const PeekFont *fonts, uint32_t k, uint8_t *rows) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) {
+    const PeekFont f = fonts[i];
+    uint8_t *row = rows + (size_t)kPeekBytes * i;
+    for (int q = 0; q < 36; q++) row[q] = f.glyf ? f.glyf[q] : 0;
+    for (int q = 0; q < 2; q++) row[36 + q] = f.hhea34 ? f.hhea34[q] : 0;
+    row[38] = row[39] = 0;
+  }
 }
 
 }  // namespace woff2file
@@ -137,54 +154,46 @@ using namespace mib::woff2file;
 using mib::woff2dev::DevMem;
 using mib::woff2dev::Timer;
 
+using mib::woff2dev::HmtxFont;
+
+extern "C" int mib_ctx_decode_caps(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offsets, size_t k, uint8_t *d_out,
+                                   const uint64_t *out_offsets, const uint64_t *out_caps, int64_t *out_sizes, int *status,
+                                   void *stream);
+
 namespace {
 
-struct AsmHost {   // what the launch uploads: the caller keeps it until the stream is synchronised
-  std::vector<AsmDesc> descs;
-  std::vector<DirRec> recs;
-};
+uint64_t g_group_bytes = 0;      // mib_force_woff2_group_bytes (0: woff2_batch.h's default)
+double g_batch_ms[2] = {0, 0};   // the last batch call: the per-font glyf loop, the whole call (host wall time)
 
-// The two kernels over a plan that has been laid out.  src[i]: table i's bytes on the device.
-// The sfnt is left at *d_sfnt (in m); nothing is synchronised.
-int assemble_device(hipStream_t st, Timer &tm, DevMem &m, const Plan &pl, const std::vector<const uint8_t *> &src,
-                    AsmHost &host, uint8_t **d_sfnt) {
-  const uint32_t num = (uint32_t)pl.t.size();
-  std::vector<AsmDesc> &descs = host.descs;
-  std::vector<DirRec> &recs = host.recs;
-  descs.resize(num);
-  recs.resize(num);
-  uint64_t most = 1;
-  for (uint32_t i = 0; i < num; i++) {
-    const Table &t = pl.t[i];
-    descs[i] = AsmDesc{src[i], t.dst_off, t.dst_len, i == pl.head && head_adjusted(pl) ? 8u : kNoZero, 0};
-    const uint64_t tiles = ((uint64_t)t.dst_len + 3 + (t.dst_off & 15) + kAsmTile - 1) / kAsmTile;
-    most = tiles > most ? tiles : most;
-  }
-  for (uint32_t r = 0; r < num; r++) {
-    const Table &t = pl.t[pl.order[r]];
-    recs[r] = DirRec{t.tag, pl.order[r], t.dst_off, t.dst_len};
-  }
-  AsmDesc *d_descs = m.take<AsmDesc>(num);
-  DirRec *d_recs = m.take<DirRec>(num);
-  uint32_t *d_sums = m.take<uint32_t>(num);
-  uint8_t *d_out = m.take<uint8_t>((size_t)pl.sfnt_len);
-  if (!d_descs || !d_recs || !d_sums || !d_out) return MIB_E_OUT_OF_MEMORY;
-  if (hipMemcpyAsync(d_descs, descs.data(), sizeof(AsmDesc) * num, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_recs, recs.data(), sizeof(DirRec) * num, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemsetAsync(d_sums, 0, sizeof(uint32_t) * num, st) != hipSuccess)
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The two kernels over the fonts of a launch (at least one).  src of every descriptor: the
+// table's bytes on the device.  The output buffer (l.out_bytes; font f at its out_base) is left
+// at *d_out_p (in m); nothing is synchronised, and the caller keeps `l` until the stream is.
+int assemble_device(hipStream_t st, Timer &tm, DevMem &m, const Launch &l, uint8_t **d_out_p) {
+  const size_t nt = l.descs.size(), nf = l.fonts.size();
+  AsmDesc *d_descs = m.take<AsmDesc>(nt);
+  DirRec *d_recs = m.take<DirRec>(nt);
+  DirFont *d_fonts = m.take<DirFont>(nf);
+  uint32_t *d_sums = m.take<uint32_t>(nt);
+  uint8_t *d_out = m.take<uint8_t>((size_t)l.out_bytes);
+  if (!d_descs || !d_recs || !d_fonts || !d_sums || !d_out) return MIB_E_OUT_OF_MEMORY;
+  if (hipMemcpyAsync(d_descs, l.descs.data(), sizeof(AsmDesc) * nt, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(d_recs, l.recs.data(), sizeof(DirRec) * nt, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(d_fonts, l.fonts.data(), sizeof(DirFont) * nf, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(d_sums, 0, sizeof(uint32_t) * nt, st) != hipSuccess)
     return MIB_E_NO_DEVICE;
-  const uint32_t blocks = (uint32_t)(most < kAsmSpread ? most : kAsmSpread);
+  const uint32_t spread = (uint32_t)(l.most_tiles < kAsmSpread ? l.most_tiles : kAsmSpread);
   tm.start("w2file_assemble");
-  hipLaunchKernelGGL(sfnt_assemble_kernel, dim3(blocks, num), dim3(kAsmThreads), 0, st, d_descs, d_out, d_sums);
+  hipLaunchKernelGGL(sfnt_assemble_kernel, dim3((uint32_t)nt, spread), dim3(kAsmThreads), 0, st, d_descs, d_out, d_sums);
   tm.stop();
-  uint32_t range, selector, shift;
-  search_fields(num, &range, &selector, &shift);
   tm.start("w2file_directory");
-  hipLaunchKernelGGL(sfnt_directory_kernel, dim3(1), dim3(kWave), 0, st, pl.flavor, num, range, selector & 0xFFFF, shift,
-                     d_recs, d_sums, head_adjusted(pl) ? pl.t[pl.head].dst_off + 8 : kNoZero, d_out);
+  hipLaunchKernelGGL(sfnt_directory_kernel, dim3((uint32_t)nf), dim3(kWave), 0, st, d_fonts, d_recs, d_sums, d_out);
   tm.stop();
   if (hipGetLastError() != hipSuccess) return MIB_E_NO_DEVICE;
-  *d_sfnt = d_out;
+  *d_out_p = d_out;
   return 0;
 }
 
@@ -220,6 +229,35 @@ void drop(mib_buf *b) {
   b->size = 0;
 }
 
+// The plan a file of these k tables, all with the null transform, would give, before layout().
+// src_off: the table's place in the font's source bytes (misalign: from a 16-byte boundary on);
+// stream_len: how many those are.
+bool plan_of_tables(uint32_t flavor, const uint32_t *tags, const mib_span *tables, const uint8_t *misalign, size_t k,
+                    Plan *pl) {
+  if (k == 0 || k > 65535) return false;
+  pl->flavor = flavor;
+  pl->t.clear();
+  pl->glyf = pl->loca = pl->hmtx = pl->hhea = pl->head = kNoTable;
+  size_t total = 0;
+  for (size_t i = 0; i < k; i++) {
+    if ((!tables[i].data && tables[i].size) || tables[i].size > mib::woff2inv::kMaxInput || (misalign && misalign[i] > 15))
+      return false;
+    if (misalign) total = ((total + 15) & ~(size_t)15) + misalign[i];
+    const size_t at = total;
+    total += tables[i].size;
+    if (total > mib::woff2inv::kMaxInput) return false;
+    pl->t.push_back(Table{tags[i], kCopy, (uint32_t)at, (uint32_t)tables[i].size, 0, 0});
+    if (tags[i] == kHeadTag) pl->head = (uint32_t)i;
+  }
+  pl->stream_len = total;
+  pl->order.resize(k);
+  for (size_t i = 0; i < k; i++) pl->order[i] = (uint32_t)i;
+  std::sort(pl->order.begin(), pl->order.end(), [&](uint32_t a, uint32_t b) { return pl->t[a].tag < pl->t[b].tag; });
+  for (size_t i = 1; i < k; i++)
+    if (pl->t[pl->order[i]].tag == pl->t[pl->order[i - 1]].tag) return false;
+  return layout(pl, 0, 0, 0);
+}
+
 }  // namespace
 
 extern "C" int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt) {
@@ -234,7 +272,7 @@ extern "C" int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt) {
   int rc = 0;
   bool timed = false;
   DevMem m;
-  AsmHost host;
+  Launch host;
   Timer tm{use.c, st, false, {}};
   do {
     uint8_t *d_comp = m.take<uint8_t>(pl.comp_len), *d_stream = m.take<uint8_t>((size_t)pl.stream_len);
@@ -270,7 +308,7 @@ extern "C" int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt) {
         rc = MIB_E_NO_DEVICE;
         break;
       }
-      if ((rc = mib::woff2dev::reconstruct_glyf_device(st, tm, m, hdr, d_stream + g.src_off, g.src_len, &d_glyf, &glyf_b,
+      if ((rc = mib::woff2dev::reconstruct_glyf_device(st, tm, m, m, hdr, d_stream + g.src_off, g.src_len, &d_glyf, &glyf_b,
                                                        &d_loca, &loca_b)))
         break;
       if (hmtx_transformed(pl)) {
@@ -292,17 +330,12 @@ extern "C" int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt) {
           break;
       }
     }
-    if (!layout(&pl, glyf_b, loca_b, hmtx_b)) {
+    if (!layout(&pl, glyf_b, loca_b, hmtx_b) || !add_font(&host, pl, FontSrc{d_stream, d_glyf, d_loca, d_hmtx})) {
       rc = MIB_E_INVALID_ARG;
       break;
     }
-    std::vector<const uint8_t *> src(pl.t.size());
-    for (size_t i = 0; i < pl.t.size(); i++) {
-      const Table &t = pl.t[i];
-      src[i] = t.kind == kGlyf ? d_glyf : t.kind == kLoca ? d_loca : t.kind == kHmtx ? d_hmtx : d_stream + t.src_off;
-    }
     uint8_t *d_sfnt = nullptr;
-    if ((rc = assemble_device(st, tm, m, pl, src, host, &d_sfnt))) break;
+    if ((rc = assemble_device(st, tm, m, host, &d_sfnt))) break;
     if ((rc = download(st, d_sfnt, (size_t)pl.sfnt_len, sfnt))) break;
     timed = true;
   } while (0);
@@ -312,43 +345,322 @@ extern "C" int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt) {
   return rc;
 }
 
+namespace {
+
+struct BatchFont {   // a file of the group whose stream decoded
+  size_t slot;       // in the call's arrays
+  Plan *pl;
+  const uint8_t *d_stream;
+  const uint8_t *hdr;   // the transformed glyf table's first 36 bytes (host), where it has one
+  uint32_t nhm;
+  uint8_t *d_glyf, *d_loca, *d_hmtx;
+  size_t glyf_b, loca_b, hmtx_b;
+  long hm;             // its place in the hmtx launch, or -1
+  uint64_t out_base;
+  bool alive;
+};
+
+// One group: files idx[0..n) of the call, all parsed.  Non-zero: the call fails.
+int decode_group(mib_ctx *c, hipStream_t st, const mib_span *files, std::vector<Plan> &plans, const size_t *idx, size_t n,
+                 mib_buf *sfnt, int *status) {
+  std::vector<const Plan *> pp(n);
+  for (size_t i = 0; i < n; i++) pp[i] = &plans[idx[i]];
+  const StreamPack pack = pack_streams(pp.data(), n);
+  std::vector<uint8_t> comp((size_t)pack.in_off[n]);
+  for (size_t i = 0; i < n; i++)
+    if (pp[i]->comp_len) memcpy(comp.data() + pack.in_off[i], files[idx[i]].data + pp[i]->comp_off, pp[i]->comp_len);
+  // what the launches read from the host until the stream is synchronised
+  std::vector<int64_t> sizes(n);
+  std::vector<int> dec(n);
+  std::vector<BatchFont> fonts;
+  std::vector<PeekFont> peek;
+  std::vector<uint8_t> rows;
+  std::vector<HmtxFont> hm;
+  std::vector<int> hm_bad;
+  Launch launch;
+  int rc = 0;
+  bool timed = false;
+  DevMem gm;   // the group's buffers: streams, reconstructed tables, outputs
+  Timer tm{c, st, false, {}};
+  do {
+    uint8_t *d_comp = gm.take<uint8_t>(comp.size()), *d_streams = gm.take<uint8_t>((size_t)pack.stream_bytes);
+    if (!d_comp || !d_streams) {
+      rc = MIB_E_OUT_OF_MEMORY;
+      break;
+    }
+    if (!comp.empty() && hipMemcpyAsync(d_comp, comp.data(), comp.size(), hipMemcpyHostToDevice, st) != hipSuccess) {
+      rc = MIB_E_NO_DEVICE;
+      break;
+    }
+    // every stream has to decode to exactly its directory's total: that is its capacity
+    rc = mib_ctx_decode_caps(c, d_comp, pack.in_off.data(), n, d_streams, pack.slot_off.data(), pack.cap.data(),
+                             sizes.data(), dec.data(), st);
+    if (rc && rc != MIB_E_NEED_SPACE) break;
+    rc = 0;
+    tm.on = mib_ctx_profiling(c) == 1;   // (the decode started the context's kernel times afresh)
+    for (size_t i = 0; i < n; i++) {
+      int s = dec[i];
+      if (s == MIB_E_NEED_SPACE || (s == 0 && (uint64_t)sizes[i] != pp[i]->stream_len)) s = MIB_E_INVALID_ARG;
+      status[idx[i]] = s;
+      if (s) continue;
+      Plan *pl = &plans[idx[i]];
+      const bool short_glyf = glyf_transformed(*pl) && pl->t[pl->glyf].src_len < (uint32_t)mib::woff2inv::kHeaderBytes;
+      if (short_glyf) {
+        status[idx[i]] = MIB_E_INVALID_ARG;
+        continue;
+      }
+      fonts.push_back(BatchFont{idx[i], pl, d_streams + pack.slot_off[i], nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, -1, 0, true});
+    }
+    // the headers the host sizes the reconstructed tables from: one launch, one read-back
+    for (const BatchFont &f : fonts)
+      if (glyf_transformed(*f.pl))
+        peek.push_back(PeekFont{f.d_stream + f.pl->t[f.pl->glyf].src_off,
+                                hmtx_transformed(*f.pl) ? f.d_stream + f.pl->t[f.pl->hhea].src_off + 34 : nullptr});
+    if (!peek.empty()) {
+      PeekFont *d_peek = gm.take<PeekFont>(peek.size());
+      uint8_t *d_rows = gm.take<uint8_t>(kPeekBytes * peek.size());
+      if (!d_peek || !d_rows) {
+        rc = MIB_E_OUT_OF_MEMORY;
+        break;
+      }
+      rows.resize(kPeekBytes * peek.size());
+      hipMemcpyAsync(d_peek, peek.data(), sizeof(PeekFont) * peek.size(), hipMemcpyHostToDevice, st);
+      tm.start("w2file_peek");
+      hipLaunchKernelGGL(w2file_peek_kernel, dim3((uint32_t)((peek.size() + 255) / 256)), dim3(256), 0, st, d_peek,
+                         (uint32_t)peek.size(), d_rows);
+      tm.stop();
+      hipMemcpyAsync(rows.data(), d_rows, rows.size(), hipMemcpyDeviceToHost, st);
+      if (hipStreamSynchronize(st) != hipSuccess) {
+        rc = MIB_E_NO_DEVICE;
+        break;
+      }
+      size_t q = 0;
+      for (BatchFont &f : fonts)
+        if (glyf_transformed(*f.pl)) {
+          f.hdr = rows.data() + kPeekBytes * q++;
+          f.nhm = ((uint32_t)f.hdr[36] << 8) | f.hdr[37];
+        }
+    }
+    // glyf and loca, font after font: a font's temporaries go before the next one's come
+    const auto loop0 = std::chrono::steady_clock::now();
+    for (BatchFont &f : fonts) {
+      if (!glyf_transformed(*f.pl)) continue;
+      const Table &g = f.pl->t[f.pl->glyf];
+      DevMem tmp;
+      const int r = mib::woff2dev::reconstruct_glyf_device(st, tm, tmp, gm, f.hdr, f.d_stream + g.src_off, g.src_len,
+                                                           &f.d_glyf, &f.glyf_b, &f.d_loca, &f.loca_b);
+      hipStreamSynchronize(st);   // (its last kernels read the temporaries)
+      if (r == MIB_E_NO_DEVICE) {
+        rc = r;
+        break;
+      }
+      if (r) {
+        status[f.slot] = r;
+        f.alive = false;
+      }
+    }
+    g_batch_ms[0] += ms_since(loop0);
+    if (rc) break;
+    // hmtx: every font that has a transformed one, in one launch
+    size_t hm_bytes = 0;
+    uint32_t most_ng = 0;
+    std::vector<size_t> hm_at;
+    for (BatchFont &f : fonts) {
+      if (!f.alive || !hmtx_transformed(*f.pl)) continue;
+      const Table &h = f.pl->t[f.pl->hmtx];
+      const uint32_t ng = ((uint32_t)f.hdr[4] << 8) | f.hdr[5];
+      uint32_t long_loca = 0;
+      if (!mib::woff2inv::hmtx_shape_ok(h.src_len, f.glyf_b, f.loca_b, ng, f.nhm, &long_loca)) {
+        status[f.slot] = MIB_E_INVALID_ARG;
+        f.alive = false;
+        continue;
+      }
+      f.hm = (long)hm.size();
+      f.hmtx_b = 4 * (size_t)f.nhm + 2 * (size_t)(ng - f.nhm);
+      hm.push_back(HmtxFont{f.d_stream + h.src_off, h.src_len, f.d_glyf, f.d_loca, nullptr, (uint32_t)f.glyf_b, long_loca, ng, f.nhm});
+      hm_at.push_back(hm_bytes);
+      hm_bytes = (hm_bytes + f.hmtx_b + 15) & ~(size_t)15;
+      most_ng = ng > most_ng ? ng : most_ng;
+    }
+    int *d_hm_bad = nullptr;
+    if (!hm.empty()) {
+      uint8_t *d_hm_out = gm.take<uint8_t>(hm_bytes);
+      HmtxFont *d_hm = gm.take<HmtxFont>(hm.size());
+      d_hm_bad = gm.take<int>(hm.size());
+      if (!d_hm_out || !d_hm || !d_hm_bad) {
+        rc = MIB_E_OUT_OF_MEMORY;
+        break;
+      }
+      for (size_t q = 0; q < hm.size(); q++) hm[q].out = d_hm_out + hm_at[q];
+      for (BatchFont &f : fonts)
+        if (f.alive && f.hm >= 0) f.d_hmtx = hm[(size_t)f.hm].out;
+      hm_bad.assign(hm.size(), 0);
+      hipMemsetAsync(d_hm_bad, 0, sizeof(int) * hm.size(), st);
+      hipMemcpyAsync(d_hm, hm.data(), sizeof(HmtxFont) * hm.size(), hipMemcpyHostToDevice, st);
+      mib::woff2dev::launch_hmtx(st, tm, d_hm, hm.size(), most_ng, d_hm_bad);
+    }
+    // layout per font, then the two assembly kernels once over every font
+    for (BatchFont &f : fonts) {
+      if (!f.alive) continue;
+      if (!layout(f.pl, f.glyf_b, f.loca_b, f.hmtx_b) || !add_font(&launch, *f.pl, FontSrc{f.d_stream, f.d_glyf, f.d_loca, f.d_hmtx})) {
+        status[f.slot] = MIB_E_INVALID_ARG;
+        f.alive = false;
+        continue;
+      }
+      f.out_base = launch.fonts.back().out_base;
+    }
+    if (!launch.fonts.empty()) {
+      uint8_t *d_out = nullptr;
+      if ((rc = assemble_device(st, tm, gm, launch, &d_out))) break;
+      for (BatchFont &f : fonts) {
+        if (!f.alive) continue;
+        mib_buf *b = &sfnt[f.slot];
+        b->data = mib_buf_alloc((size_t)f.pl->sfnt_len);
+        if (!b->data) {
+          status[f.slot] = MIB_E_OUT_OF_MEMORY;
+          f.alive = false;
+          continue;
+        }
+        b->size = (size_t)f.pl->sfnt_len;
+        hipMemcpyAsync(b->data, d_out + f.out_base, b->size, hipMemcpyDeviceToHost, st);
+      }
+    }
+    if (d_hm_bad) hipMemcpyAsync(hm_bad.data(), d_hm_bad, sizeof(int) * hm.size(), hipMemcpyDeviceToHost, st);
+    if (hipStreamSynchronize(st) != hipSuccess) {
+      rc = MIB_E_NO_DEVICE;
+      break;
+    }
+    // flags that do not fit the size; a loca entry that does not fit the glyf table
+    for (BatchFont &f : fonts)
+      if (f.alive && f.hm >= 0 && hm_bad[(size_t)f.hm]) {
+        drop(&sfnt[f.slot]);
+        status[f.slot] = MIB_E_INVALID_ARG;
+      }
+    timed = true;
+  } while (0);
+  if (rc) hipStreamSynchronize(st);   // nothing of this group is in flight when its buffers go
+  tm.collect(timed);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" int mib_woff2_decode_batch(const mib_span *files, size_t k, mib_buf *sfnt, int *status) {
+  if (k == 0) return 0;
+  if (sfnt)
+    for (size_t i = 0; i < k; i++) sfnt[i].data = nullptr, sfnt[i].size = 0;
+  if (!files || !sfnt || !status) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++)
+    if (!files[i].data && files[i].size) return MIB_E_INVALID_ARG;
+  const auto call0 = std::chrono::steady_clock::now();
+  std::vector<Plan> plans(k);
+  std::vector<size_t> parsed;   // (before anything is allocated on the device)
+  std::vector<uint64_t> lens;
+  for (size_t i = 0; i < k; i++) {
+    status[i] = parse(files[i].data, files[i].size, &plans[i]) ? 0 : MIB_E_INVALID_ARG;
+    if (status[i]) continue;
+    parsed.push_back(i);
+    lens.push_back(plans[i].stream_len);
+  }
+  if (parsed.empty()) return 0;
+  DefaultCall use;   // (the lock is recursive: the decode below runs on this context inside it)
+  if (!use.c) return MIB_E_NO_DEVICE;
+  g_batch_ms[0] = 0;
+  int rc = 0;
+  for (const Group &g : make_groups(lens, g_group_bytes))
+    if ((rc = decode_group(use.c, use.st, files, plans, &parsed[g.first], g.count, sfnt, status))) break;
+  if (rc)
+    for (size_t i = 0; i < k; i++) drop(&sfnt[i]);
+  g_batch_ms[1] = ms_since(call0);
+  return rc;
+}
+
+extern "C" void mib_force_woff2_group_bytes(uint64_t bytes) { g_group_bytes = bytes; }
+
+// diagnostic (DESIGN.md's measurements): host wall time of the last mib_woff2_decode_batch that
+// reached the device -- its per-font glyf reconstruct loops, and the whole call
+extern "C" void mib_woff2_batch_last_ms(double out[2]) {
+  out[0] = g_batch_ms[0];
+  out[1] = g_batch_ms[1];
+}
+
 extern "C" int mib_debug_sfnt_assemble(uint32_t flavor, const uint32_t *tags, const mib_span *tables,
                                        const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt) {
   if (!sfnt) return MIB_E_INVALID_ARG;
   sfnt->data = nullptr;
   sfnt->size = 0;
   if (k == 0 || k > 65535 || !tags || !tables) return MIB_E_INVALID_ARG;
-  // the plan a file of these tables, all with the null transform, would give
   Plan pl;
-  pl.flavor = flavor;
-  pl.glyf = pl.loca = pl.hmtx = pl.hhea = pl.head = kNoTable;
-  std::vector<size_t> at(k);   // each table's place in the source buffer
-  size_t total = 0;
-  for (size_t i = 0; i < k; i++) {
-    if ((!tables[i].data && tables[i].size) || tables[i].size > mib::woff2inv::kMaxInput ||
-        (d_src_misalign && d_src_misalign[i] > 15))
-      return MIB_E_INVALID_ARG;
-    if (d_src_misalign) total = ((total + 15) & ~(size_t)15) + d_src_misalign[i];
-    at[i] = total;
-    total += tables[i].size;
-    if (total > mib::woff2inv::kMaxInput) return MIB_E_INVALID_ARG;
-    pl.t.push_back(Table{tags[i], kCopy, (uint32_t)at[i], (uint32_t)tables[i].size, 0, 0});
-    if (tags[i] == kHeadTag) pl.head = (uint32_t)i;
-  }
-  pl.stream_len = total;
-  pl.order.resize(k);
-  for (size_t i = 0; i < k; i++) pl.order[i] = (uint32_t)i;
-  std::sort(pl.order.begin(), pl.order.end(), [&](uint32_t a, uint32_t b) { return pl.t[a].tag < pl.t[b].tag; });
-  for (size_t i = 1; i < k; i++)
-    if (pl.t[pl.order[i]].tag == pl.t[pl.order[i - 1]].tag) return MIB_E_INVALID_ARG;
-  if (!layout(&pl, 0, 0, 0)) return MIB_E_INVALID_ARG;
+  if (!plan_of_tables(flavor, tags, tables, d_src_misalign, k, &pl)) return MIB_E_INVALID_ARG;
   DefaultCall use;
   if (!use.c) return MIB_E_NO_DEVICE;
   hipStream_t st = use.st;
   int rc = 0;
   bool timed = false;
   DevMem m;
-  AsmHost host;
+  Launch host;
+  Timer tm{use.c, st, mib_ctx_profiling(use.c) == 1, {}};
+  do {
+    uint8_t *d_src = m.take<uint8_t>((size_t)pl.stream_len);
+    if (!d_src) {
+      rc = MIB_E_OUT_OF_MEMORY;
+      break;
+    }
+    bool ok = true;
+    for (size_t i = 0; i < k; i++)
+      if (tables[i].size)
+        ok = ok && hipMemcpyAsync(d_src + pl.t[i].src_off, tables[i].data, tables[i].size, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (!ok) {
+      rc = MIB_E_NO_DEVICE;
+      break;
+    }
+    if (!add_font(&host, pl, FontSrc{d_src, nullptr, nullptr, nullptr})) {
+      rc = MIB_E_INVALID_ARG;
+      break;
+    }
+    uint8_t *d_sfnt = nullptr;
+    if ((rc = assemble_device(st, tm, m, host, &d_sfnt))) break;
+    if ((rc = download(st, d_sfnt, (size_t)pl.sfnt_len, sfnt))) break;
+    timed = true;
+  } while (0);
+  if (rc) hipStreamSynchronize(st);
+  tm.collect(timed);
+  if (rc) drop(sfnt);
+  return rc;
+}
+
+extern "C" int mib_debug_sfnt_assemble_batch(const uint32_t *flavors, const uint32_t *counts, const uint32_t *tags,
+                                             const mib_span *tables, const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt) {
+  if (k == 0) return 0;
+  if (sfnt)
+    for (size_t f = 0; f < k; f++) sfnt[f].data = nullptr, sfnt[f].size = 0;
+  if (!flavors || !counts || !tags || !tables || !sfnt) return MIB_E_INVALID_ARG;
+  // every font's source bytes from a 16-byte boundary of one buffer on, staged on the host
+  std::vector<Plan> plans(k);
+  std::vector<size_t> base(k);
+  size_t first = 0, total = 0;
+  for (size_t f = 0; f < k; f++) {
+    if (!plan_of_tables(flavors[f], tags + first, tables + first, d_src_misalign ? d_src_misalign + first : nullptr, counts[f],
+                        &plans[f]))
+      return MIB_E_INVALID_ARG;
+    base[f] = total = (total + 15) & ~(size_t)15;
+    total += (size_t)plans[f].stream_len;
+    first += counts[f];
+  }
+  std::vector<uint8_t> stage(total);
+  first = 0;
+  for (size_t f = 0; f < k; f++) {
+    for (size_t i = 0; i < counts[f]; i++)
+      if (tables[first + i].size) memcpy(stage.data() + base[f] + plans[f].t[i].src_off, tables[first + i].data, tables[first + i].size);
+    first += counts[f];
+  }
+  DefaultCall use;
+  if (!use.c) return MIB_E_NO_DEVICE;
+  hipStream_t st = use.st;
+  int rc = 0;
+  bool timed = false;
+  DevMem m;
+  Launch host;
   Timer tm{use.c, st, mib_ctx_profiling(use.c) == 1, {}};
   do {
     uint8_t *d_src = m.take<uint8_t>(total);
@@ -356,24 +668,31 @@ extern "C" int mib_debug_sfnt_assemble(uint32_t flavor, const uint32_t *tags, co
       rc = MIB_E_OUT_OF_MEMORY;
       break;
     }
-    std::vector<const uint8_t *> src(k);
-    bool ok = true;
-    for (size_t i = 0; i < k; i++) {
-      src[i] = d_src + at[i];
-      if (tables[i].size)
-        ok = ok && hipMemcpyAsync(d_src + at[i], tables[i].data, tables[i].size, hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-    if (!ok) {
+    if (total && hipMemcpyAsync(d_src, stage.data(), total, hipMemcpyHostToDevice, st) != hipSuccess) {
       rc = MIB_E_NO_DEVICE;
       break;
     }
-    uint8_t *d_sfnt = nullptr;
-    if ((rc = assemble_device(st, tm, m, pl, src, host, &d_sfnt))) break;
-    if ((rc = download(st, d_sfnt, (size_t)pl.sfnt_len, sfnt))) break;
+    for (size_t f = 0; f < k && !rc; f++)
+      if (!add_font(&host, plans[f], FontSrc{d_src + base[f], nullptr, nullptr, nullptr})) rc = MIB_E_INVALID_ARG;
+    if (rc) break;
+    uint8_t *d_out = nullptr;
+    if ((rc = assemble_device(st, tm, m, host, &d_out))) break;
+    for (size_t f = 0; f < k; f++) {
+      sfnt[f].data = mib_buf_alloc((size_t)plans[f].sfnt_len);
+      if (!sfnt[f].data) {
+        rc = MIB_E_OUT_OF_MEMORY;
+        break;
+      }
+      sfnt[f].size = (size_t)plans[f].sfnt_len;
+      hipMemcpyAsync(sfnt[f].data, d_out + host.fonts[f].out_base, sfnt[f].size, hipMemcpyDeviceToHost, st);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = MIB_E_NO_DEVICE;
+    if (rc) break;
     timed = true;
   } while (0);
   if (rc) hipStreamSynchronize(st);
   tm.collect(timed);
-  if (rc) drop(sfnt);
+  if (rc)
+    for (size_t f = 0; f < k; f++) drop(&sfnt[f]);
   return rc;
 }

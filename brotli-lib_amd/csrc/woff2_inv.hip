@@ -338,16 +338,19 @@ __global__ void inv_loca_kernel(uint32_t ng, uint32_t long_loca, const uint32_t 
   if (i <= ng) put_loca(loca, long_loca, i, off[i]);
 }
 
-// (n >= 1: the table's flags are its first byte)
-__global__ void inv_hmtx_kernel(const uint8_t *t, uint64_t n, const uint8_t *glyf, uint32_t glyf_n, const uint8_t *loca,
-                                uint32_t long_loca, uint32_t ng, uint32_t nhm, uint8_t *out, int *bad) {
+// blockIdx.y (and on by gridDim.y): the font; blockIdx.x: its glyphs.  (n >= 1: the table's flags
+// are its first byte)
+__global__ void inv_hmtx_kernel(const mib::woff2dev::HmtxFont *fonts, uint32_t k, int *bad) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= ng) return;
-  if (!hmtx_flags_ok(t[0], n, ng, nhm)) {   // nothing behind the flags is read then
-    atomicOr(bad, 1);
-    return;
+  for (uint32_t f = blockIdx.y; f < k; f += gridDim.y) {
+    const mib::woff2dev::HmtxFont d = fonts[f];
+    if (g >= d.ng) continue;
+    if (!hmtx_flags_ok(d.t[0], d.n, d.ng, d.nhm)) {   // nothing behind the flags is read then
+      atomicOr(bad + f, 1);
+      continue;
+    }
+    if (!hmtx_glyph(d.t, d.glyf, d.glyf_n, d.loca, d.long_loca, d.ng, d.nhm, g, d.out)) atomicOr(bad + f, 1);
   }
-  if (!hmtx_glyph(t, glyf, glyf_n, loca, long_loca, ng, nhm, g, out)) atomicOr(bad, 1);
 }
 
 }  // namespace woff2inv
@@ -355,6 +358,7 @@ __global__ void inv_hmtx_kernel(const uint8_t *t, uint64_t n, const uint8_t *gly
 
 using namespace mib::woff2inv;
 using mib::woff2dev::DevMem;
+using mib::woff2dev::HmtxFont;
 using mib::woff2dev::Timer;
 
 namespace {
@@ -376,9 +380,9 @@ extern "C" void mib_woff2_inv_last_steps(uint32_t out[2]) {
   out[1] = g_last_steps[1];
 }
 
-int mib::woff2dev::reconstruct_glyf_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *hdr, const uint8_t *d_t,
-                                           size_t n, uint8_t **d_glyf, size_t *glyf_b_out, uint8_t **d_loca,
-                                           size_t *loca_b_out) {
+int mib::woff2dev::reconstruct_glyf_device(hipStream_t st, Timer &tm, DevMem &m, DevMem &keep, const uint8_t *hdr,
+                                           const uint8_t *d_t, size_t n, uint8_t **d_glyf, size_t *glyf_b_out,
+                                           uint8_t **d_loca, size_t *loca_b_out) {
   View hv, v;
   if (!parse_header(hdr, n, hdr, &hv) || !parse_header(hdr, n, d_t, &v)) return MIB_E_INVALID_ARG;
   const uint32_t ng = hv.num_glyphs;
@@ -460,7 +464,7 @@ int mib::woff2dev::reconstruct_glyf_device(hipStream_t st, Timer &tm, DevMem &m,
   if (bad || !totals_ok(hv, end, total)) return MIB_E_INVALID_ARG;
   // the size comes from the sizing pass alone (every glyph empty: one zero byte, as fontTools)
   const size_t glyf_b = total ? total : 1, loca_b = g1 * (hv.long_loca ? 4 : 2);
-  uint8_t *d_out = m.take<uint8_t>(glyf_b + loca_b);
+  uint8_t *d_out = keep.take<uint8_t>(glyf_b + loca_b);
   if (!d_out) return MIB_E_OUT_OF_MEMORY;
   if (!total) hipMemsetAsync(d_out, 0, 1, st);
   tm.start("w2inv_write");
@@ -504,7 +508,7 @@ extern "C" int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_bu
         break;
       }
       hipMemcpyAsync(d_t, tglyf, n, hipMemcpyHostToDevice, st);
-      if ((rc = mib::woff2dev::reconstruct_glyf_device(st, tm, m, tglyf, d_t, n, &d_glyf, &glyf_b, &d_loca, &loca_b))) break;
+      if ((rc = mib::woff2dev::reconstruct_glyf_device(st, tm, m, m, tglyf, d_t, n, &d_glyf, &glyf_b, &d_loca, &loca_b))) break;
       glyf->data = mib_buf_alloc(glyf_b);
       loca->data = mib_buf_alloc(loca_b);
       if (!glyf->data || !loca->data) {
@@ -534,18 +538,25 @@ extern "C" int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_bu
   return rc;
 }
 
+void mib::woff2dev::launch_hmtx(hipStream_t st, Timer &tm, const HmtxFont *d_fonts, size_t k, uint32_t most_ng, int *d_bad) {
+  const uint32_t rows = (uint32_t)(k < 65535 ? k : 65535);   // (the kernel walks on by gridDim.y)
+  tm.start("w2inv_hmtx");
+  hipLaunchKernelGGL(inv_hmtx_kernel, dim3((most_ng + 255) / 256, rows), dim3(256), 0, st, d_fonts, (uint32_t)k, d_bad);
+  tm.stop();
+}
+
 int mib::woff2dev::reconstruct_hmtx_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *d_t, size_t n,
                                            const uint8_t *d_glyf, size_t glyf_n, const uint8_t *d_loca, uint32_t long_loca,
                                            uint32_t ng, uint32_t nhm, uint8_t **d_out_p, size_t *out_b) {
   const size_t total = 4 * (size_t)nhm + 2 * (size_t)(ng - nhm);
   uint8_t *d_out = m.take<uint8_t>(total);
   int *d_bad = m.take<int>(1);
-  if (!d_out || !d_bad) return MIB_E_OUT_OF_MEMORY;
+  HmtxFont *d_font = m.take<HmtxFont>(1);
+  if (!d_out || !d_bad || !d_font) return MIB_E_OUT_OF_MEMORY;
+  const HmtxFont font{d_t, (uint64_t)n, d_glyf, d_loca, d_out, (uint32_t)glyf_n, long_loca, ng, nhm};
   hipMemsetAsync(d_bad, 0, 4, st);
-  tm.start("w2inv_hmtx");
-  hipLaunchKernelGGL(inv_hmtx_kernel, dim3((ng + 255) / 256), dim3(256), 0, st, d_t, (uint64_t)n, d_glyf, (uint32_t)glyf_n,
-                     d_loca, long_loca, ng, nhm, d_out, d_bad);
-  tm.stop();
+  hipMemcpyAsync(d_font, &font, sizeof(font), hipMemcpyHostToDevice, st);   // (synchronised below)
+  launch_hmtx(st, tm, d_font, 1, ng, d_bad);
   int bad = 0;
   hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
   if (hipStreamSynchronize(st) != hipSuccess) return MIB_E_NO_DEVICE;

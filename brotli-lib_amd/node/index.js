@@ -176,10 +176,15 @@ function woff2ReconstructHmtx(data, glyf, loca, numGlyphs, numHMetrics) {
 function woff2Decode(data) {
   return toU8(native.woff2File(data))
 }
+// many .woff2 files in shared launches: per slot the sfnt woff2Decode(file) alone would have
+// returned, or the Error it would have thrown (not thrown here: the other files go on)
+function woff2DecodeBatch(files) {
+  return native.woff2FileBatch(files).map((o) => (o instanceof Error ? o : toU8(o)))
+}
 
 module.exports = {
   brotliEncode, BrotliEncoder, brotliDecode, BrotliDecoder, brotliDecodedSize, EncoderMode,
   brotliEncodeBatch, brotliEncodeBatchAsync, brotliDecodeBatchAsync,
   brotliDecoderUpdateBatch, brotliDecoderFinishBatch,
-  woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx, woff2Decode,
+  woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx, woff2Decode, woff2DecodeBatch,
 }

@@ -19,7 +19,7 @@ import os
 __all__ = ['brotliEncode', 'BrotliEncoder', 'brotliDecode', 'BrotliDecoder', 'brotliDecodedSize', 'EncoderMode', 'BrotliError',
            'encode_batch', 'decode_batch', 'encoder_update_batch', 'decoder_update_batch', 'decoder_finish_batch',
            'decoder_update_batch_device', 'decoder_finish_batch_device', 'MORE_OUTPUT', 'DeviceContext', 'library_path',
-           'woff2_decode']
+           'woff2_decode', 'woff2_decode_batch']
 
 _PKG = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # BROTLI_AMD_LIB: an instrumented build of the same library (timing experiments only)
@@ -197,6 +197,16 @@ def _L():
             lib.mib_debug_sfnt_assemble.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                                                     ctypes.POINTER(_Span), ctypes.c_char_p, ctypes.c_size_t,
                                                     ctypes.POINTER(_Buf)]
+        if hasattr(lib, 'mib_woff2_decode_batch'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_woff2_decode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Buf),
+                                                   ctypes.POINTER(ctypes.c_int)]
+            lib.mib_force_woff2_group_bytes.argtypes = [ctypes.c_uint64]
+            lib.mib_force_woff2_group_bytes.restype = None
+            lib.mib_debug_sfnt_assemble_batch.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                                          ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_Span),
+                                                          ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
+            lib.mib_woff2_batch_last_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
+            lib.mib_woff2_batch_last_ms.restype = None
         lib.mib_part_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         if hasattr(lib, 'mib_debug_match_records'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_debug_match_records.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
@@ -671,6 +681,71 @@ def debug_sfnt_assemble(flavor, tables, misalign=None):
     if rc:
         raise _err(rc)
     return _take(buf)
+
+
+def woff2_decode_batch(files):
+    """woff2_decode of many files in shared launches (mib_woff2_decode_batch): the Brotli streams
+    decode in one launch and the sfnts are assembled in one.  Returns a list with, per slot, the
+    bytes woff2_decode(file) alone would have returned, or the BrotliError it would have raised
+    (not raised here: the other files go on).  The same file may stand in several slots."""
+    keep = [_in(b) for b in files]
+    k = len(keep)
+    spans = (_Span * max(k, 1))(*[_Span(_addr(a) if n else None, n) for a, n, _ in keep])
+    outs = (_Buf * max(k, 1))()
+    st = (ctypes.c_int * max(k, 1))()
+    rc = _L().mib_woff2_decode_batch(spans, k, outs, st)
+    if rc:
+        raise _err(rc)
+    return [_err(st[i]) if st[i] else _take(outs[i]) for i in range(k)]
+
+
+def force_woff2_group_bytes(n):
+    """Diagnostic (tests): woff2_decode_batch works its files in groups whose decompressed streams
+    sum to at most n bytes (0: the default); a larger file is a group alone."""
+    _L().mib_force_woff2_group_bytes(int(n))
+
+
+def woff2_batch_last_ms():
+    """Diagnostic (measurements): (the per-font glyf reconstruct loops, the whole call) of the last
+    woff2_decode_batch that reached the device, host wall time in ms."""
+    out = (ctypes.c_double * 2)()
+    _L().mib_woff2_batch_last_ms(out)
+    return out[0], out[1]
+
+
+def debug_sfnt_assemble_batch(fonts, misalign=None):
+    """Diagnostic (tests): woff2_decode_batch's assembly kernels alone over fonts =
+    [(flavor, [(tag, bytes)])]; misalign: per font None or a list as debug_sfnt_assemble takes
+    (None: every font packed back to back).  Returns the list of sfnts."""
+    fonts = [(int(flavor) & 0xFFFFFFFF, [(bytes(tag), _bytes(data)) for tag, data in tables]) for flavor, tables in fonts]
+    k = len(fonts)
+    flat = [t for _, tables in fonts for t in tables]
+    n = len(flat)
+    if any(len(tag) != 4 for tag, _ in flat) or (misalign is not None and len(misalign) != k):
+        raise _err(-101)   # MIB_E_INVALID_ARG
+    mis = None
+    if misalign is not None:
+        per = [list(m) if m is not None else [0] * len(tables) for m, (_, tables) in zip(misalign, fonts)]
+        if any(len(m) != len(tables) for m, (_, tables) in zip(per, fonts)):
+            raise _err(-101)
+        mis = bytes(v for m in per for v in m)
+    flavors = (ctypes.c_uint32 * max(k, 1))(*[f for f, _ in fonts])
+    counts = (ctypes.c_uint32 * max(k, 1))(*[len(tables) for _, tables in fonts])
+    tags = (ctypes.c_uint32 * max(n, 1))(*[int.from_bytes(tag, 'big') for tag, _ in flat])
+    blob = b''.join(data for _, data in flat)
+    keep = ctypes.create_string_buffer(blob, max(len(blob), 1))
+    base = ctypes.addressof(keep)
+    spans = (_Span * max(n, 1))()
+    at = 0
+    for i, (_, data) in enumerate(flat):
+        spans[i].data = base + at
+        spans[i].size = len(data)
+        at += len(data)
+    outs = (_Buf * max(k, 1))()
+    rc = _L().mib_debug_sfnt_assemble_batch(flavors, counts, tags, spans, mis, k, outs)
+    if rc:
+        raise _err(rc)
+    return [_take(outs[i]) for i in range(k)]
 
 
 def part_stats(ctx=None):

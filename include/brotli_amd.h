@@ -320,6 +320,28 @@ int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt);
  * WOFF2 stream). */
 int mib_debug_sfnt_assemble(uint32_t flavor, const uint32_t *tags, const mib_span *tables,
                             const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt);
+/* k single-font .woff2 files -> their sfnts, in shared launches (DESIGN.md 4c "A batch of
+ * files"): the Brotli streams of a group of files decode in one launch, the sfnts of a group are
+ * assembled in one launch of each assembly kernel; glyf and loca are reconstructed font after
+ * font.  sfnt[i] / status[i] are what mib_woff2_decode(files[i]) alone would have produced, byte
+ * for byte and code for code: everything about one file (a container that does not parse, a
+ * corrupt stream, a table the reconstruct functions reject) is that slot's status -- 0,
+ * MIB_E_INVALID_ARG, the decoder's own negative code, or MIB_E_OUT_OF_MEMORY when the slot's host
+ * buffer could not be allocated -- and leaves the others running; a slot with a non-zero status
+ * has sfnt[i] = {NULL, 0}.  The same file may stand in several slots.  Returns 0, or
+ * MIB_E_INVALID_ARG (a NULL array with k > 0, NULL data with a size: checked before anything
+ * else), MIB_E_NO_DEVICE, MIB_E_OUT_OF_MEMORY (a group's device buffers); then every sfnt[i] is
+ * {NULL, 0}.  k == 0, and a call none of whose files parses, need no device.  Holds the default
+ * context's lock for its duration.  Profiling: every group's decode starts the context's kernel
+ * times afresh, so after a call of more than one group the times are the last group's. */
+int mib_woff2_decode_batch(const mib_span *files, size_t k, mib_buf *sfnt, int *status);
+/* Diagnostic (tests): the files of a call are worked in groups whose decompressed streams sum to
+ * at most this many bytes (0: the default, 512 MiB); a file larger than that is a group alone. */
+void mib_force_woff2_group_bytes(uint64_t bytes);
+/* Diagnostic (tests): the batch's assembly kernels alone over k fonts; font f has counts[f]
+ * tables, taken in order from tags / tables / d_src_misalign (as mib_debug_sfnt_assemble). */
+int mib_debug_sfnt_assemble_batch(const uint32_t *flavors, const uint32_t *counts, const uint32_t *tags,
+                                  const mib_span *tables, const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt);
 
 /* Part-parallel decoding (streams this encoder marked with a part index):
  * how many streams a context (NULL: the default one) decoded part-parallel, and how many of
