@@ -960,6 +960,8 @@ void mib_encode_ws_free(void *p) {
   delete ws;
 }
 int mib_live_encoders(void) { return g_live_encoders.load(); }
+// the output room mib_encode_batch gives a stream of n bytes (woff2_write.hip sizes its own with it)
+uint64_t mib_encode_out_bound(uint64_t n) { return out_bound(n); }
 // the default context after a host call: a workspace above `keep` bytes is released
 void mib_encode_ws_trim(void **p, uint64_t keep) {   // (the hysteresis of runtime.cpp release_large)
   Workspace *ws = reinterpret_cast<Workspace *>(*p);

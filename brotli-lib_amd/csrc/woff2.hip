@@ -9,6 +9,11 @@
 // per-stream counts are scanned; `glyf_write_kernel` parses again and writes each glyph's
 // bytes at its offsets.  The byte choices follow fontTools 4.62 (`WOFF2GlyfTable`), the
 // implementation the tests compare against (tests/test_gpu_woff2.py).
+//
+// Each transform is a core over device pointers (woff2_dev.h: a sizing step and a write step
+// that writes the whole table, header included, at any device address) and a host wrapper
+// around it, mib_woff2_transform_glyf / _hmtx; the file writer (woff2_write.hip) runs the cores
+// on the font it has uploaded and lets them write into its stream buffer.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdio.h>
@@ -18,6 +23,7 @@
 #include <vector>
 
 #include "common.h"
+#include "woff2_dev.h"
 
 namespace mib {
 namespace woff2 {
@@ -336,14 +342,17 @@ __global__ void glyf_sizes_kernel(Font f, uint32_t *sizes /* [kStreams][n] */, u
   bits[g] = (uint8_t)((k.overlap ? 1 : 0) | (k.bbox ? 2 : 0));
 }
 
-// offs: exclusive scans of sizes; base[s] = the stream's offset in the output
-__global__ void glyf_write_kernel(Font f, const uint32_t *offs, const uint32_t *base, uint8_t *out) {
+// offs: exclusive scans of sizes; base.v[s] = the stream's offset in the output
+struct StreamBase {
+  uint32_t v[kStreams];
+};
+__global__ void glyf_write_kernel(Font f, const uint32_t *offs, StreamBase base, uint8_t *out) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= f.num_glyphs) return;
   Sink k;
   for (int i = 0; i < kStreams; i++) {
     const uint32_t extra = i == kBBox ? ((f.num_glyphs + 31) >> 5) << 2 : 0;   // the bbox bitmap comes first
-    k.s[i] = out + base[i] + extra + offs[(size_t)i * f.num_glyphs + g];
+    k.s[i] = out + (uint32_t)(base.v[i] + extra + offs[(size_t)i * f.num_glyphs + g]);
   }
   walk_glyph(f, g, k);
 }
@@ -370,6 +379,14 @@ __global__ void glyf_bitmaps_kernel(uint32_t n, const uint8_t *bits, uint8_t *bb
   }
 }
 
+// the transformed table's 36-byte header, stated by the host once the streams' sizes are known;
+// byte stores: the table may lie at any address
+struct GlyfHeader {
+  uint8_t b[kHeaderBytes];
+};
+__global__ void glyf_header_kernel(GlyfHeader h, uint8_t *out) {
+  if (threadIdx.x < kHeaderBytes) out[threadIdx.x] = h.b[threadIdx.x];
+}
 
 // ---------------------------------------------------------------- hmtx (WOFF2 section 5.4)
 // fontTools WOFF2HmtxTable.transform: the proportional (i < numberOfHMetrics) and monospaced
@@ -388,6 +405,7 @@ __global__ void hmtx_check_kernel(Font f, const uint8_t *hmtx, uint32_t nhm, uin
 __global__ void hmtx_write_kernel(uint32_t ng, const uint8_t *hmtx, uint32_t nhm, uint32_t keep, uint8_t *out) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= ng) return;
+  if (g == 0) out[0] = (uint8_t)((keep == 1 ? 0 : 1) | (keep == 2 ? 0 : 2));   // set: that array is absent
   if (g < nhm) {
     out[1 + 2 * g] = hmtx[4 * g];
     out[2 + 2 * g] = hmtx[4 * g + 1];
@@ -403,13 +421,13 @@ __global__ void hmtx_write_kernel(uint32_t ng, const uint8_t *hmtx, uint32_t nhm
 }
 
 }  // namespace woff2
-}  // namespace mib
+
+// ---------------------------------------------------------------- the cores (woff2_dev.h)
+namespace woff2dev {
 
 using namespace mib::woff2;
 
 namespace {
-uint32_t hbe16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
-uint32_t hbe32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 void put16(uint8_t *p, uint32_t v) {
   p[0] = (uint8_t)(v >> 8);
   p[1] = (uint8_t)v;
@@ -420,13 +438,142 @@ void put32(uint8_t *p, uint32_t v) {
   p[2] = (uint8_t)(v >> 8);
   p[3] = (uint8_t)v;
 }
+Font font_of(const GlyfIn &in) { return Font{in.d_glyf, in.glyf_len, in.d_loca, in.num_glyphs, (int32_t)in.long_loca}; }
+}  // namespace
+
+int transform_glyf_size(hipStream_t st, Timer &tm, DevMem &m, const GlyfIn &in, GlyfSized *z) {
+  const uint32_t ng = in.num_glyphs;
+  const size_t nsz = (size_t)kStreams * ng;
+  uint32_t *d_sizes = m.take<uint32_t>(nsz), *d_offs = m.take<uint32_t>(nsz);
+  uint8_t *d_bits = m.take<uint8_t>(ng);
+  int *d_bad = m.take<int>(1);
+  if (!d_sizes || !d_offs || !d_bits || !d_bad) return MIB_E_OUT_OF_MEMORY;
+  hipMemsetAsync(d_bad, 0, 4, st);
+  const Font f = font_of(in);
+  const dim3 grid((ng + 255) / 256), block(256);
+  tm.start("w2enc_glyf_sizes");
+  hipLaunchKernelGGL(glyf_sizes_kernel, grid, block, 0, st, f, d_sizes, d_bits, d_bad);
+  tm.stop();
+  // exclusive scan of every stream's per-glyph sizes (one flat scan: each stream's run
+  // starts at its own total, subtracted below)
+  size_t tmp_b = 0;
+  hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_b, d_sizes, d_offs, (int)nsz, st);
+  uint8_t *d_tmp = m.take<uint8_t>(tmp_b);
+  if (!d_tmp) return MIB_E_OUT_OF_MEMORY;
+  tm.start("w2enc_glyf_scan");
+  hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_b, d_sizes, d_offs, (int)nsz, st);
+  tm.stop();
+  uint32_t starts[kStreams + 1], tot[kStreams];
+  int bad = 0;
+  uint32_t last_off = 0, last_size = 0;
+  std::vector<uint8_t> bits(ng);   // the overlap bitmap only when some simple glyph has the flag
+  for (int s = 0; s < kStreams; s++) hipMemcpyAsync(&starts[s], d_offs + (size_t)s * ng, 4, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(&last_off, d_offs + nsz - 1, 4, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(&last_size, d_sizes + nsz - 1, 4, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(bits.data(), d_bits, ng, hipMemcpyDeviceToHost, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return MIB_E_NO_DEVICE;
+  if (bad) return MIB_E_INVALID_ARG;   // a malformed glyph
+  starts[kStreams] = last_off + last_size;
+  for (int s = 0; s < kStreams; s++) tot[s] = starts[s + 1] - starts[s];
+  const uint32_t bbm = ((ng + 31) >> 5) << 2;
+  tot[kBBox] += bbm;
+  // output layout: header, the streams, (overlap bitmap); each stream's glyph offsets are
+  // the flat scan minus the stream's start
+  uint64_t pos = kHeaderBytes;
+  for (int s = 0; s < kStreams; s++) {
+    z->base[s] = (uint32_t)(pos - starts[s]);
+    pos += tot[s];
+  }
+  bool ovl = false;
+  for (uint32_t g = 0; g < ng; g++) ovl = ovl || (bits[g] & 1);
+  z->in = in;
+  z->d_offs = d_offs;
+  z->d_bits = d_bits;
+  z->bbox_at = z->base[kBBox] + starts[kBBox];
+  z->streams_end = pos;
+  z->overlap = ovl;
+  z->total = pos + (ovl ? ((ng + 7) >> 3) : 0);
+  put16(&z->header[0], 0);
+  put16(&z->header[2], ovl ? 1 : 0);
+  put16(&z->header[4], ng);
+  put16(&z->header[6], in.long_loca ? 1 : 0);
+  for (int s = 0; s < kStreams; s++) put32(&z->header[8 + 4 * s], tot[s]);
+  return 0;
+}
+
+void transform_glyf_write(hipStream_t st, Timer &tm, const GlyfSized &z, uint8_t *d_out) {
+  const uint32_t ng = z.in.num_glyphs, bbm = ((ng + 31) >> 5) << 2;
+  const Font f = font_of(z.in);
+  StreamBase base;
+  for (int s = 0; s < kStreams; s++) base.v[s] = z.base[s];
+  GlyfHeader h;
+  memcpy(h.b, z.header, kHeaderBytes);
+  tm.start("w2enc_glyf_write");
+  hipLaunchKernelGGL(glyf_header_kernel, dim3(1), dim3(64), 0, st, h, d_out);
+  hipLaunchKernelGGL(glyf_write_kernel, dim3((ng + 255) / 256), dim3(256), 0, st, f, z.d_offs, base, d_out);
+  hipLaunchKernelGGL(glyf_bitmaps_kernel, dim3((bbm + 255) / 256), dim3(256), 0, st, ng, z.d_bits, d_out + z.bbox_at,
+                     d_out + z.streams_end, z.overlap ? 1 : 0);
+  tm.stop();
+}
+
+int transform_hmtx_size(hipStream_t st, Timer &tm, DevMem &m, const GlyfIn &in, const uint8_t *d_hmtx, uint32_t nhm,
+                        HmtxSized *z) {
+  uint32_t *d_mis = m.take<uint32_t>(1);
+  if (!d_mis) return MIB_E_OUT_OF_MEMORY;
+  hipMemsetAsync(d_mis, 0, 4, st);
+  const uint32_t ng = in.num_glyphs;
+  tm.start("w2enc_hmtx_check");
+  hipLaunchKernelGGL(hmtx_check_kernel, dim3((ng + 255) / 256), dim3(256), 0, st, font_of(in), d_hmtx, nhm, d_mis);
+  tm.stop();
+  uint32_t mis = 0;
+  hipMemcpyAsync(&mis, d_mis, 4, hipMemcpyDeviceToHost, st);
+  if (hipStreamSynchronize(st) != hipSuccess) return MIB_E_NO_DEVICE;
+  z->num_glyphs = ng;
+  z->d_hmtx = d_hmtx;
+  z->nhm = nhm;
+  z->keep = mis;   // 0: none, 1: proportional lsbs, 2: monospaced lsbs, 3: both needed -- no transform
+  z->total = mis == 3 ? 0 : 1 + 2ull * nhm + (mis == 1 ? 2ull * nhm : mis == 2 ? 2ull * (ng - nhm) : 0);
+  return 0;
+}
+
+void transform_hmtx_write(hipStream_t st, Timer &tm, const HmtxSized &z, uint8_t *d_out) {
+  tm.start("w2enc_hmtx_write");
+  hipLaunchKernelGGL(hmtx_write_kernel, dim3((z.num_glyphs + 255) / 256), dim3(256), 0, st, z.num_glyphs, z.d_hmtx, z.nhm,
+                     z.keep, d_out);
+  tm.stop();
+}
+
+}  // namespace woff2dev
+}  // namespace mib
+
+using mib::woff2dev::DevMem;
+using mib::woff2dev::GlyfIn;
+using mib::woff2dev::GlyfSized;
+using mib::woff2dev::HmtxSized;
+using mib::woff2dev::Timer;
+
+namespace {
+uint32_t hbe16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
+uint32_t hbe32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+// a transform's result, from device memory into a fresh mib_buf
+int download(hipStream_t st, const uint8_t *d_out, uint64_t total, mib_buf *out) {
+  out->data = mib_buf_alloc(total);
+  if (!out->data) return MIB_E_OUT_OF_MEMORY;
+  out->size = total;
+  hipMemcpyAsync(out->data, d_out, total, hipMemcpyDeviceToHost, st);
+  if (hipStreamSynchronize(st) != hipSuccess) {
+    mib_buf_free(out);
+    out->data = nullptr;
+    out->size = 0;
+    return MIB_E_NO_DEVICE;
+  }
+  return 0;
+}
 }  // namespace
 
 extern "C" int mib_ctx_ready(mib_ctx *c);
-extern "C" mib_ctx *mib_default_ctx(void);
-extern "C" void mib_default_lock(int on);
-extern "C" void *mib_ctx_stream_of(mib_ctx *c);
-extern "C" int mib_ctx_device_of(mib_ctx *c);
 
 extern "C" int mib_woff2_transform_glyf(const uint8_t *ttf, size_t n, mib_buf *out) {
   if (!out || (!ttf && n)) return MIB_E_INVALID_ARG;
@@ -460,104 +607,30 @@ extern "C" int mib_woff2_transform_glyf(const uint8_t *ttf, size_t n, mib_buf *o
   hipSetDevice(mib_ctx_device_of(c));
   hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
   int rc = 0;
-  uint8_t *d_font = nullptr, *d_bits = nullptr, *d_out = nullptr, *d_tmp = nullptr;
-  uint32_t *d_sizes = nullptr, *d_offs = nullptr, *d_base = nullptr;
-  int *d_bad = nullptr;
-  const size_t nsz = (size_t)kStreams * ng;
-  std::vector<uint32_t> tot(kStreams);
-  std::vector<uint8_t> host;
-  do {
-    if (hipMalloc(&d_font, glyf_len + loca_len + 16) != hipSuccess || hipMalloc(&d_sizes, 4 * nsz) != hipSuccess ||
-        hipMalloc(&d_offs, 4 * nsz) != hipSuccess || hipMalloc(&d_bits, ng) != hipSuccess ||
-        hipMalloc(&d_bad, 4) != hipSuccess || hipMalloc(&d_base, 4 * kStreams) != hipSuccess) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    hipMemcpyAsync(d_font, ttf + glyf_off, glyf_len, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_font + glyf_len, ttf + loca_off, loca_len, hipMemcpyHostToDevice, st);
-    hipMemsetAsync(d_bad, 0, 4, st);
-    Font f{d_font, (uint32_t)glyf_len, d_font + glyf_len, ng, long_loca};
-    const dim3 grid((ng + 255) / 256), block(256);
-    hipLaunchKernelGGL(glyf_sizes_kernel, grid, block, 0, st, f, d_sizes, d_bits, d_bad);
-    // exclusive scan of every stream's per-glyph sizes (one flat scan: each stream's run
-    // starts at its own total, subtracted below)
-    size_t tmp_b = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_b, d_sizes, d_offs, (int)nsz, st);
-    if (hipMalloc(&d_tmp, tmp_b + 16) != hipSuccess) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_b, d_sizes, d_offs, (int)nsz, st);
-    std::vector<uint32_t> starts(kStreams + 1);
-    int bad = 0;
-    uint32_t last_off = 0, last_size = 0;
-    for (int s = 0; s < kStreams; s++) hipMemcpyAsync(&starts[s], d_offs + (size_t)s * ng, 4, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(&last_off, d_offs + nsz - 1, 4, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(&last_size, d_sizes + nsz - 1, 4, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) {
-      rc = MIB_E_NO_DEVICE;
-      break;
-    }
-    if (bad) {
-      rc = MIB_E_INVALID_ARG;   // a malformed glyph
-      break;
-    }
-    starts[kStreams] = last_off + last_size;
-    for (int s = 0; s < kStreams; s++) tot[s] = starts[s + 1] - starts[s];
-    const uint32_t bbm = ((ng + 31) >> 5) << 2;
-    tot[kBBox] += bbm;
-    // output layout: header, the streams, (overlap bitmap); each stream's glyph offsets are
-    // the flat scan minus the stream's start
-    std::vector<uint32_t> base(kStreams);
-    uint64_t pos = kHeaderBytes;
-    for (int s = 0; s < kStreams; s++) {
-      base[s] = (uint32_t)(pos - starts[s]);   // (unsigned wrap: base + flat offset = position)
-      pos += tot[s];
-    }
-    // the overlap bitmap only when some simple glyph has the flag (decided after the sizes pass)
-    std::vector<uint8_t> bits(ng);
-    hipMemcpyAsync(bits.data(), d_bits, ng, hipMemcpyDeviceToHost, st);
-    hipStreamSynchronize(st);
-    bool ovl = false;
-    for (uint32_t g = 0; g < ng; g++) ovl = ovl || (bits[g] & 1);
-    const uint64_t total = pos + (ovl ? ((ng + 7) >> 3) : 0);
-    if (hipMalloc(&d_out, total + 16) != hipSuccess) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    hipMemcpyAsync(d_base, base.data(), 4 * kStreams, hipMemcpyHostToDevice, st);
-    hipLaunchKernelGGL(glyf_write_kernel, grid, block, 0, st, f, d_offs, d_base, d_out);
-    const uint32_t bbox_at = (uint32_t)(base[kBBox] + starts[kBBox]);
-    hipLaunchKernelGGL(glyf_bitmaps_kernel, dim3((bbm + 255) / 256), dim3(256), 0, st, ng, d_bits, d_out + bbox_at,
-                       d_out + pos, ovl ? 1 : 0);
-    host.resize(total);
-    hipMemcpyAsync(host.data(), d_out, total, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) {
-      rc = MIB_E_NO_DEVICE;
-      break;
-    }
-    put16(&host[0], 0);
-    put16(&host[2], ovl ? 1 : 0);
-    put16(&host[4], ng);
-    put16(&host[6], long_loca ? 1 : 0);
-    for (int s = 0; s < kStreams; s++) put32(&host[8 + 4 * s], tot[s]);
-    out->data = mib_buf_alloc(total);
-    if (!out->data) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    memcpy(out->data, host.data(), total);
-    out->size = total;
-  } while (0);
-  hipFree(d_font);
-  hipFree(d_sizes);
-  hipFree(d_offs);
-  hipFree(d_bits);
-  hipFree(d_bad);
-  hipFree(d_base);
-  hipFree(d_out);
-  hipFree(d_tmp);
+  {
+    DevMem m;
+    Timer tm{c, st, false, {}};
+    do {
+      uint8_t *d_font = m.take<uint8_t>(glyf_len + loca_len);
+      if (!d_font) {
+        rc = MIB_E_OUT_OF_MEMORY;
+        break;
+      }
+      hipMemcpyAsync(d_font, ttf + glyf_off, glyf_len, hipMemcpyHostToDevice, st);
+      hipMemcpyAsync(d_font + glyf_len, ttf + loca_off, loca_len, hipMemcpyHostToDevice, st);
+      GlyfSized z;
+      if ((rc = mib::woff2dev::transform_glyf_size(st, tm, m, GlyfIn{d_font, (uint32_t)glyf_len, d_font + glyf_len, ng, (uint32_t)long_loca}, &z)))
+        break;
+      uint8_t *d_out = m.take<uint8_t>((size_t)z.total);
+      if (!d_out) {
+        rc = MIB_E_OUT_OF_MEMORY;
+        break;
+      }
+      mib::woff2dev::transform_glyf_write(st, tm, z, d_out);
+      rc = download(st, d_out, z.total, out);
+    } while (0);
+    hipStreamSynchronize(st);   // nothing of this call is in flight when its buffers go
+  }
   mib_default_lock(0);
   return rc;
 }
@@ -598,53 +671,35 @@ extern "C" int mib_woff2_transform_hmtx(const uint8_t *ttf, size_t n, mib_buf *o
   hipSetDevice(mib_ctx_device_of(c));
   hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
   int rc = 0;
-  uint8_t *d_font = nullptr, *d_out = nullptr;
-  uint32_t *d_mis = nullptr;
-  do {
-    const uint64_t gl = len[0], ll = len[1], hl = len[5];
-    if (hipMalloc(&d_font, gl + ll + hl + 16) != hipSuccess || hipMalloc(&d_mis, 4) != hipSuccess) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    hipMemcpyAsync(d_font, ttf + off[0], gl, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_font + gl, ttf + off[1], ll, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_font + gl + ll, ttf + off[5], hl, hipMemcpyHostToDevice, st);
-    hipMemsetAsync(d_mis, 0, 4, st);
-    Font f{d_font, (uint32_t)gl, d_font + gl, ng, long_loca};
-    const dim3 grid((ng + 255) / 256), block(256);
-    hipLaunchKernelGGL(hmtx_check_kernel, grid, block, 0, st, f, d_font + gl + ll, nhm, d_mis);
-    uint32_t mis = 0;
-    hipMemcpyAsync(&mis, d_mis, 4, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) {
-      rc = MIB_E_NO_DEVICE;
-      break;
-    }
-    if (mis == 3) break;   // both arrays needed: no transform
-    const uint32_t keep = mis;   // 0: none, 1: proportional lsbs, 2: monospaced lsbs
-    const uint64_t total = 1 + 2ull * nhm + (keep == 1 ? 2ull * nhm : keep == 2 ? 2ull * (ng - nhm) : 0);
-    if (hipMalloc(&d_out, total + 16) != hipSuccess) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    hipLaunchKernelGGL(hmtx_write_kernel, grid, block, 0, st, ng, d_font + gl + ll, nhm, keep, d_out);
-    out->data = mib_buf_alloc(total);
-    if (!out->data) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    out->size = total;
-    hipMemcpyAsync(out->data, d_out, total, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) {
-      mib_buf_free(out);
-      rc = MIB_E_NO_DEVICE;
-      break;
-    }
-    out->data[0] = (uint8_t)((keep == 1 ? 0 : 1) | (keep == 2 ? 0 : 2));   // set: that array is absent
-    out->size = total;
-  } while (0);
-  hipFree(d_font);
-  hipFree(d_mis);
-  hipFree(d_out);
+  {
+    DevMem m;
+    Timer tm{c, st, false, {}};
+    do {
+      const uint64_t gl = len[0], ll = len[1], hl = len[5];
+      uint8_t *d_font = m.take<uint8_t>(gl + ll + hl);
+      if (!d_font) {
+        rc = MIB_E_OUT_OF_MEMORY;
+        break;
+      }
+      hipMemcpyAsync(d_font, ttf + off[0], gl, hipMemcpyHostToDevice, st);
+      hipMemcpyAsync(d_font + gl, ttf + off[1], ll, hipMemcpyHostToDevice, st);
+      hipMemcpyAsync(d_font + gl + ll, ttf + off[5], hl, hipMemcpyHostToDevice, st);
+      HmtxSized z;
+      if ((rc = mib::woff2dev::transform_hmtx_size(st, tm, m, GlyfIn{d_font, (uint32_t)gl, d_font + gl, ng, (uint32_t)long_loca},
+                                                   d_font + gl + ll, nhm, &z)))
+        break;
+      if (!z.total) break;   // both arrays needed: no transform
+      uint8_t *d_out = m.take<uint8_t>((size_t)z.total);
+      if (!d_out) {
+        rc = MIB_E_OUT_OF_MEMORY;
+        break;
+      }
+      mib::woff2dev::transform_hmtx_write(st, tm, z, d_out);
+      rc = download(st, d_out, z.total, out);
+    } while (0);
+    hipStreamSynchronize(st);
+  }
   mib_default_lock(0);
   return rc;
 }
+

@@ -1,5 +1,6 @@
-// What the WOFF2 host entry points (woff2_inv.hip, woff2_file.hip) share: a call's device
-// buffers, its per-kernel timer, and the reconstruct cores that work on device memory.
+// What the WOFF2 host entry points (woff2.hip, woff2_inv.hip, woff2_file.hip, woff2_write.hip)
+// share: a call's device buffers, its per-kernel timer, and the transform and reconstruct cores
+// that work on device memory.
 #ifndef MIB_WOFF2_DEV_H_
 #define MIB_WOFF2_DEV_H_
 #include <hip/hip_runtime.h>
@@ -95,6 +96,45 @@ struct HmtxFont {
 // fit its size or whose loca does not fit its glyf.  Nothing is synchronised.
 void launch_hmtx(hipStream_t st, Timer &tm, const HmtxFont *d_fonts, size_t k, uint32_t most_ng, int *d_bad);
 
+// The transform cores (woff2.hip): what mib_woff2_transform_glyf / _hmtx do between upload and
+// download, and what the file writer (woff2_write.hip) runs per font.  Each has a sizing step,
+// which synchronises the stream and tells how many bytes the table takes, and a write step, which
+// writes them -- the 36-byte header and the hmtx flag byte included -- at a device address of any
+// alignment and synchronises nothing.  The caller holds the default context's lock and has set its
+// device; what the sizing step took from `m` has to live until the write step's kernels are done.
+struct GlyfIn {   // glyf and loca on the device, any alignment; loca holds num_glyphs + 1 entries
+  const uint8_t *d_glyf;
+  uint32_t glyf_len;
+  const uint8_t *d_loca;
+  uint32_t num_glyphs, long_loca;
+};
+struct GlyfSized {
+  GlyfIn in;
+  const uint32_t *d_offs;   // the scanned per-glyph stream sizes
+  const uint8_t *d_bits;    // per glyph: overlap-simple, explicit bbox
+  uint32_t base[7], bbox_at;
+  uint64_t streams_end;
+  bool overlap;
+  uint64_t total;           // the transformed table's bytes
+  uint8_t header[36];
+};
+//   MIB_E_INVALID_ARG: a malformed glyph
+int transform_glyf_size(hipStream_t st, Timer &tm, DevMem &m, const GlyfIn &in, GlyfSized *z);
+void transform_glyf_write(hipStream_t st, Timer &tm, const GlyfSized &z, uint8_t *d_out);
+struct HmtxSized {
+  const uint8_t *d_hmtx;
+  uint32_t num_glyphs, nhm, keep;
+  uint64_t total;   // 0: both side-bearing arrays differ from the glyphs' xMin -- no transform
+};
+//   d_hmtx: at least 4 nhm + 2 (num_glyphs - nhm) bytes, 1 <= nhm <= num_glyphs
+int transform_hmtx_size(hipStream_t st, Timer &tm, DevMem &m, const GlyfIn &in, const uint8_t *d_hmtx, uint32_t nhm,
+                        HmtxSized *z);
+void transform_hmtx_write(hipStream_t st, Timer &tm, const HmtxSized &z, uint8_t *d_out);
+
 }  // namespace woff2dev
+
+namespace woff2file {
+uint64_t forced_group_bytes();   // mib_force_woff2_group_bytes' value (woff2_file.hip)
+}
 }  // namespace mib
 #endif

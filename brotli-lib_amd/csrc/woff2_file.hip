@@ -576,6 +576,7 @@ extern "C" int mib_woff2_decode_batch(const mib_span *files, size_t k, mib_buf *
 }
 
 extern "C" void mib_force_woff2_group_bytes(uint64_t bytes) { g_group_bytes = bytes; }
+uint64_t mib::woff2file::forced_group_bytes() { return g_group_bytes; }   // (the writer's groups: woff2_write.hip)
 
 // diagnostic (DESIGN.md's measurements): host wall time of the last mib_woff2_decode_batch that
 // reached the device -- its per-font glyf reconstruct loops, and the whole call

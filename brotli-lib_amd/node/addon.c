@@ -670,6 +670,77 @@ static napi_value js_woff2_file_batch(napi_env env, napi_callback_info info) {
   free(res), free(st);
   return out;
 }
+/* woff2Write(sfnt, quality, lgwin, transforms) -> Buffer: the .woff2 file of a single-font sfnt,
+ * written on the GPU (mib_woff2_encode); a font that does not parse throws (MIB_E_INVALID_ARG) */
+static void woff2_enc_opts(napi_env env, size_t argc, napi_value *argv, mib_woff2_enc_opts *o) {
+  o->quality = get_int(env, argc > 1 ? argv[1] : NULL, 11);
+  o->lgwin = get_int(env, argc > 2 ? argv[2] : NULL, 22);
+  o->transforms = (uint32_t)get_i64(env, argc > 3 ? argv[3] : NULL, MIB_WOFF2_GLYF | MIB_WOFF2_HMTX);
+}
+static napi_value js_woff2_write(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  const uint8_t *p;
+  size_t n;
+  if (argc < 1 || get_bytes(env, argv[0], &p, &n)) {
+    napi_throw_type_error(env, NULL, "input must be a Uint8Array");
+    return NULL;
+  }
+  mib_woff2_enc_opts o;
+  woff2_enc_opts(env, argc, argv, &o);
+  mib_buf b = {0, 0};
+  const int rc = mib_woff2_encode(n ? p : NULL, n, &o, &b);
+  if (rc) return throw_code(env, rc);
+  return take(env, &b);
+}
+/* woff2WriteBatch([bytes...], quality, lgwin, transforms) -> one Buffer or Error per font: the
+ * fonts are uploaded, copied and compressed in shared launches (mib_woff2_encode_batch) */
+static napi_value js_woff2_write_batch(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  uint32_t k = 0;
+  bool is_arr = false;
+  if (argc < 1 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) {
+    napi_throw_type_error(env, NULL, "woff2EncodeBatch(sfnts: Uint8Array[], options?)");
+    return NULL;
+  }
+  CHECK(env, napi_get_array_length(env, argv[0], &k));
+  mib_woff2_enc_opts o;
+  woff2_enc_opts(env, argc, argv, &o);
+  mib_span *in = (mib_span *)calloc(k ? k : 1, sizeof(mib_span));
+  mib_buf *res = (mib_buf *)calloc(k ? k : 1, sizeof(mib_buf));
+  int *st = (int *)calloc(k ? k : 1, sizeof(int));
+  for (uint32_t i = 0; i < k; i++) {
+    napi_value e;
+    napi_get_element(env, argv[0], i, &e);
+    if (get_bytes(env, e, &in[i].data, &in[i].size)) {
+      free(in), free(res), free(st);
+      napi_throw_type_error(env, NULL, "every font must be a Uint8Array");
+      return NULL;
+    }
+    if (!in[i].size) in[i].data = NULL;
+  }
+  const int rc = mib_woff2_encode_batch(in, k, &o, res, st);
+  free(in);
+  if (rc) {
+    free(res), free(st);
+    return throw_code(env, rc);
+  }
+  napi_create_array_with_length(env, k, &out);
+  for (uint32_t i = 0; i < k; i++) {
+    napi_value v = st[i] ? decoder_error(env, st[i], &res[i]) : take(env, &res[i]);
+    if (!v) {
+      for (uint32_t j = i + 1; j < k; j++) mib_buf_free(&res[j]);
+      out = NULL;
+      break;
+    }
+    napi_set_element(env, out, i, v);
+  }
+  free(res), free(st);
+  return out;
+}
 /* woff2InvGlyf(data) -> [glyf, loca] (Buffers): the TrueType tables of a WOFF2-transformed glyf
  * table, computed on the GPU; a table that does not parse throws (MIB_E_INVALID_ARG) */
 static napi_value js_woff2_inv_glyf(napi_env env, napi_callback_info info) {
@@ -744,6 +815,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"woff2InvHmtx", 0, js_woff2_inv_hmtx, 0, 0, 0, napi_default, 0},
       {"woff2File", 0, js_woff2_file, 0, 0, 0, napi_default, 0},
       {"woff2FileBatch", 0, js_woff2_file_batch, 0, 0, 0, napi_default, 0},
+      {"woff2Write", 0, js_woff2_write, 0, 0, 0, napi_default, 0},
+      {"woff2WriteBatch", 0, js_woff2_write_batch, 0, 0, 0, napi_default, 0},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -91,3 +91,17 @@ export declare function woff2ReconstructHmtx(data: Uint8Array, glyf: Uint8Array,
 export declare function woff2Decode(data: Uint8Array): Uint8Array
 /** woff2Decode of many files in shared GPU launches (one Brotli decode launch and one assembly launch per group of files): per slot the sfnt, or the Error woff2Decode(file) alone would have thrown */
 export declare function woff2DecodeBatch(files: Uint8Array[]): (Uint8Array | Error)[]
+export interface Woff2EncodeOptions {
+  /** 0..11, default 11 */
+  quality?: number
+  /** 10..24, default 22 */
+  lgwin?: number
+  /** transform glyf + loca where the font has them (default true); a font the transform rejects throws */
+  transformGlyf?: boolean
+  /** transform hmtx where glyf is transformed and a side-bearing array equals the glyphs' xMin (default true) */
+  transformHmtx?: boolean
+}
+/** a single-font sfnt -> its .woff2 file, written on the GPU (FONT-mode Brotli; tables in tag order, DSIG dropped; every byte but the Brotli stream is fixed); woff2Decode reads every file written; throws on a font that does not parse */
+export declare function woff2Encode(sfnt: Uint8Array, options?: Woff2EncodeOptions): Uint8Array
+/** woff2Encode of many fonts in shared GPU launches (one upload, one copy launch and one encode call per group of fonts): per slot the file, or the Error woff2Encode(font) alone would have thrown */
+export declare function woff2EncodeBatch(sfnts: Uint8Array[], options?: Woff2EncodeOptions): (Uint8Array | Error)[]

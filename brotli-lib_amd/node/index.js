@@ -181,10 +181,30 @@ function woff2Decode(data) {
 function woff2DecodeBatch(files) {
   return native.woff2FileBatch(files).map((o) => (o instanceof Error ? o : toU8(o)))
 }
+// a single-font sfnt -> its .woff2 file, written on the GPU: glyf, loca and hmtx transformed, the
+// other tables copied beside them, the stream compressed in FONT mode; every byte but the Brotli
+// stream is fixed (tables in tag order, DSIG dropped) and woff2Decode reads every file written.
+// options: { quality, lgwin, transformGlyf, transformHmtx } (both transforms default to true)
+function woff2EncodeArgs(options) {
+  const o = options || {}
+  const q = o.quality === undefined || o.quality === null ? 11 : Math.max(0, Math.min(11, o.quality | 0))
+  const w = o.lgwin === undefined || o.lgwin === null ? 22 : Math.max(10, Math.min(24, o.lgwin | 0))
+  const t = (o.transformGlyf === false ? 0 : 1) | (o.transformHmtx === false ? 0 : 2)
+  return [q, w, t]
+}
+function woff2Encode(sfnt, options) {
+  return toU8(native.woff2Write(sfnt, ...woff2EncodeArgs(options)))
+}
+// many fonts in shared launches: per slot the file woff2Encode(font) alone would have returned,
+// or the Error it would have thrown (not thrown here: the other fonts go on)
+function woff2EncodeBatch(sfnts, options) {
+  return native.woff2WriteBatch(sfnts, ...woff2EncodeArgs(options)).map((o) => (o instanceof Error ? o : toU8(o)))
+}
 
 module.exports = {
   brotliEncode, BrotliEncoder, brotliDecode, BrotliDecoder, brotliDecodedSize, EncoderMode,
   brotliEncodeBatch, brotliEncodeBatchAsync, brotliDecodeBatchAsync,
   brotliDecoderUpdateBatch, brotliDecoderFinishBatch,
   woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx, woff2Decode, woff2DecodeBatch,
+  woff2Encode, woff2EncodeBatch,
 }

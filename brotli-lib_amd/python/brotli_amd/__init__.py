@@ -19,7 +19,7 @@ import os
 __all__ = ['brotliEncode', 'BrotliEncoder', 'brotliDecode', 'BrotliDecoder', 'brotliDecodedSize', 'EncoderMode', 'BrotliError',
            'encode_batch', 'decode_batch', 'encoder_update_batch', 'decoder_update_batch', 'decoder_finish_batch',
            'decoder_update_batch_device', 'decoder_finish_batch_device', 'MORE_OUTPUT', 'DeviceContext', 'library_path',
-           'woff2_decode', 'woff2_decode_batch']
+           'woff2_decode', 'woff2_decode_batch', 'woff2_encode', 'woff2_encode_batch']
 
 _PKG = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # BROTLI_AMD_LIB: an instrumented build of the same library (timing experiments only)
@@ -59,6 +59,10 @@ class _Buf(ctypes.Structure):
 
 class _Span(ctypes.Structure):
     _fields_ = [('data', ctypes.c_void_p), ('size', ctypes.c_size_t)]
+
+
+class _Woff2EncOpts(ctypes.Structure):
+    _fields_ = [('quality', ctypes.c_int), ('lgwin', ctypes.c_int), ('transforms', ctypes.c_uint32)]
 
 
 class _KTime(ctypes.Structure):
@@ -207,6 +211,11 @@ def _L():
                                                           ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
             lib.mib_woff2_batch_last_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
             lib.mib_woff2_batch_last_ms.restype = None
+        if hasattr(lib, 'mib_woff2_encode'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_woff2_encode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Woff2EncOpts),
+                                             ctypes.POINTER(_Buf)]
+            lib.mib_woff2_encode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Woff2EncOpts),
+                                                   ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_part_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         if hasattr(lib, 'mib_debug_match_records'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_debug_match_records.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
@@ -694,6 +703,53 @@ def woff2_decode_batch(files):
     outs = (_Buf * max(k, 1))()
     st = (ctypes.c_int * max(k, 1))()
     rc = _L().mib_woff2_decode_batch(spans, k, outs, st)
+    if rc:
+        raise _err(rc)
+    return [_err(st[i]) if st[i] else _take(outs[i]) for i in range(k)]
+
+
+def _woff2_enc_opts(options):
+    """quality and lgwin clamped as brotliEncode's; transformGlyf / transformHmtx default to True;
+    `transforms` (the C ABI's bit set, MIB_WOFF2_GLYF 1 | MIB_WOFF2_HMTX 2) overrides both."""
+    options = options or {}
+    o = _Woff2EncOpts(11, 22, 0)
+    if options.get('quality') is not None:
+        o.quality = max(0, min(11, int(options['quality'])))
+    if options.get('lgwin') is not None:
+        o.lgwin = max(10, min(24, int(options['lgwin'])))
+    if options.get('transforms') is not None:
+        o.transforms = int(options['transforms']) & 0xFFFFFFFF
+    else:
+        o.transforms = (1 if options.get('transformGlyf', True) else 0) | (2 if options.get('transformHmtx', True) else 0)
+    return o
+
+
+def woff2_encode(sfnt, options=None):
+    """The .woff2 file (W3C WOFF2) of a single-font sfnt, written on the GPU: glyf, loca and hmtx
+    transformed, the other tables copied beside them, the stream compressed in FONT mode
+    (mib_woff2_encode).  options: quality, lgwin, transformGlyf, transformHmtx.  Every byte but the
+    Brotli stream is fixed (tables in tag order, DSIG dropped); woff2_decode reads every file
+    written.  A font that does not parse, or that the glyf transform rejects, raises BrotliError
+    (MIB_E_INVALID_ARG)."""
+    data = _bytes(sfnt)
+    buf = _Buf()
+    rc = _L().mib_woff2_encode(data, len(data), ctypes.byref(_woff2_enc_opts(options)), ctypes.byref(buf))
+    if rc:
+        raise _err(rc)
+    return _take(buf)
+
+
+def woff2_encode_batch(sfnts, options=None):
+    """woff2_encode of many fonts in shared launches (mib_woff2_encode_batch): one upload, one copy
+    launch and one encode call per group of fonts.  Returns a list with, per slot, the file or the
+    BrotliError woff2_encode(font) alone would have raised (not raised here: the other fonts go
+    on).  The same font may stand in several slots."""
+    keep = [_in(b) for b in sfnts]
+    k = len(keep)
+    spans = (_Span * max(k, 1))(*[_Span(_addr(a) if n else None, n) for a, n, _ in keep])
+    outs = (_Buf * max(k, 1))()
+    st = (ctypes.c_int * max(k, 1))()
+    rc = _L().mib_woff2_encode_batch(spans, k, ctypes.byref(_woff2_enc_opts(options)), outs, st)
     if rc:
         raise _err(rc)
     return [_err(st[i]) if st[i] else _take(outs[i]) for i in range(k)]

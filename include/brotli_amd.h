@@ -343,6 +343,46 @@ void mib_force_woff2_group_bytes(uint64_t bytes);
 int mib_debug_sfnt_assemble_batch(const uint32_t *flavors, const uint32_t *counts, const uint32_t *tags,
                                   const mib_span *tables, const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt);
 
+/* An sfnt (TrueType or CFF flavoured, single font) -> a .woff2 file (W3C WOFF2), written on the
+ * device (DESIGN.md 4c "Writing a file"): the font is uploaded once, glyf and hmtx are transformed
+ * there (as mib_woff2_transform_glyf / _hmtx do), the other tables are copied into the stream
+ * beside them, the stream is compressed in FONT mode, and the compressed bytes land behind the
+ * header and directory in the result.  Every byte of the file but the Brotli stream is fixed:
+ * tables in ascending tag order, DSIG dropped, origLength the table's length in the input font
+ * (for glyf and loca too, where the specification makes it a hint: for a font that is not
+ * already normalised the reconstructed tables, and with them totalSfntSize, may differ), head's
+ * checkSumAdjustment stored as zero and its flags bit 11 set when glyf / loca are transformed, the
+ * header's version head's fontRevision, the file zero-padded to a 4-byte boundary (counted in its
+ * length), no metadata, no private block: what fontTools writes for the same font.
+ *   transforms  MIB_WOFF2_GLYF: glyf + loca are transformed where the font has them (a font the
+ *               transform rejects -- head shorter than 54 bytes, no maxp, a short loca, numGlyphs
+ *               0, a malformed glyph -- is MIB_E_INVALID_ARG: no silent fallback);
+ *               MIB_WOFF2_HMTX: hmtx is transformed where glyf is, hhea has 36 bytes,
+ *               1 <= numberOfHMetrics <= numGlyphs, hmtx is exactly 4 nhm + 2 (ng - nhm) bytes and
+ *               a side-bearing array equals the glyphs' xMin; otherwise it is stored as it is.
+ *               Unknown bits: MIB_E_INVALID_ARG.
+ *   quality, lgwin  clamped as mib_enc_opts'.  o NULL: quality 11, lgwin 22, both transforms.
+ * MIB_E_INVALID_ARG, before any device work, for: fewer than 12 bytes; a first tag of ttcf, wOF2 or
+ * wOFF; numTables 0 or a directory past the input; a record whose offset + length runs past the
+ * input; a tag twice; table lengths above 256 MiB in sum; exactly one of glyf and loca; nothing
+ * left after dropping DSIG.  Checksums, searchRange fields, record order, alignment and overlap
+ * of the input's tables are not checked.  mib_woff2_decode accepts every file written.  On any
+ * error woff2 is {NULL, 0}.  mib_woff2_encode is the batch with k = 1. */
+typedef struct { int quality; int lgwin; uint32_t transforms; } mib_woff2_enc_opts;
+#define MIB_WOFF2_GLYF 1u   /* glyf + loca */
+#define MIB_WOFF2_HMTX 2u
+int mib_woff2_encode(const uint8_t *sfnt, size_t n, const mib_woff2_enc_opts *o, mib_buf *woff2);
+/* k fonts in shared launches: per group of fonts (mib_force_woff2_group_bytes, counting sfnt
+ * bytes) one upload, one copy launch over every untransformed table, one encode call over every
+ * stream, one synchronisation for the downloads; the transforms run font after font.  woff2[i] /
+ * status[i] as mib_woff2_decode_batch's: everything about one font is that slot's status (0,
+ * MIB_E_INVALID_ARG, MIB_E_OUT_OF_MEMORY for the slot's host buffer) and leaves the others
+ * running; the same font may stand in several slots.  Returns 0, or MIB_E_INVALID_ARG (a NULL
+ * array with k > 0, NULL data with a size, unknown transforms bits), MIB_E_NO_DEVICE,
+ * MIB_E_OUT_OF_MEMORY (a group's device buffers); then every woff2[i] is {NULL, 0}.  k == 0, and a
+ * call in which no font parses, need no device.  Holds the default context's lock. */
+int mib_woff2_encode_batch(const mib_span *sfnts, size_t k, const mib_woff2_enc_opts *o, mib_buf *woff2, int *status);
+
 /* Part-parallel decoding (streams this encoder marked with a part index):
  * how many streams a context (NULL: the default one) decoded part-parallel, and how many of
  * those it sent back to the serial decoder because a part did not check out. Diagnostic. */
