@@ -547,92 +547,68 @@ void transform_hmtx_write(hipStream_t st, Timer &tm, const HmtxSized &z, uint8_t
 }  // namespace woff2dev
 }  // namespace mib
 
-using mib::woff2dev::DevMem;
+using mib::woff2dev::Call;
 using mib::woff2dev::GlyfIn;
 using mib::woff2dev::GlyfSized;
 using mib::woff2dev::HmtxSized;
-using mib::woff2dev::Timer;
 
 namespace {
 uint32_t hbe16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
 uint32_t hbe32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
-// a transform's result, from device memory into a fresh mib_buf
-int download(hipStream_t st, const uint8_t *d_out, uint64_t total, mib_buf *out) {
-  out->data = mib_buf_alloc(total);
-  if (!out->data) return MIB_E_OUT_OF_MEMORY;
-  out->size = total;
-  hipMemcpyAsync(out->data, d_out, total, hipMemcpyDeviceToHost, st);
-  if (hipStreamSynchronize(st) != hipSuccess) {
-    mib_buf_free(out);
-    out->data = nullptr;
-    out->size = 0;
-    return MIB_E_NO_DEVICE;
+// The tables the transforms read, in the order the wrappers index them: glyf needs the first
+// four, hmtx all six.
+enum { kGlyf, kLoca, kHead, kMaxp, kHhea, kHmtx, kTags };
+const char *const kTag[kTags] = {"glyf", "loca", "head", "maxp", "hhea", "hmtx"};
+struct DirEntry {
+  uint64_t off = 0, len = 0;
+  bool have = false;
+};
+
+// One walk over the sfnt's table records (host: a few dozen bytes).  False for fewer than 12
+// bytes, a directory that runs past the input, or any record whose offset + length does;
+// otherwise out[t] is the record of kTag[t], t < count (of the last one, where a tag comes twice).
+bool scan_directory(const uint8_t *ttf, size_t n, int count, DirEntry *out) {
+  if (n < 12) return false;
+  const uint32_t ntab = hbe16(ttf + 4);
+  if (12 + 16ull * ntab > n) return false;
+  for (uint32_t i = 0; i < ntab; i++) {
+    const uint8_t *r = ttf + 12 + 16 * i;
+    const uint32_t off = hbe32(r + 8), len = hbe32(r + 12);
+    if ((uint64_t)off + len > n) return false;
+    for (int t = 0; t < count; t++)
+      if (!memcmp(r, kTag[t], 4)) out[t] = DirEntry{off, len, true};
   }
-  return 0;
+  return true;
 }
 }  // namespace
-
-extern "C" int mib_ctx_ready(mib_ctx *c);
 
 extern "C" int mib_woff2_transform_glyf(const uint8_t *ttf, size_t n, mib_buf *out) {
   if (!out || (!ttf && n)) return MIB_E_INVALID_ARG;
   out->data = nullptr;
   out->size = 0;
-  // the sfnt table directory (host: a few dozen bytes)
-  if (n < 12) return MIB_E_INVALID_ARG;
-  const uint32_t ntab = hbe16(ttf + 4);
-  if (12 + 16ull * ntab > n) return MIB_E_INVALID_ARG;
-  uint64_t glyf_off = 0, glyf_len = 0, loca_off = 0, loca_len = 0, head_off = 0, maxp_off = 0;
-  bool hg = false, hl = false, hh = false, hm = false;
-  for (uint32_t i = 0; i < ntab; i++) {
-    const uint8_t *r = ttf + 12 + 16 * i;
-    const uint32_t off = hbe32(r + 8), len = hbe32(r + 12);
-    if ((uint64_t)off + len > n) return MIB_E_INVALID_ARG;
-    if (!memcmp(r, "glyf", 4)) glyf_off = off, glyf_len = len, hg = true;
-    else if (!memcmp(r, "loca", 4)) loca_off = off, loca_len = len, hl = true;
-    else if (!memcmp(r, "head", 4)) head_off = off, hh = true;
-    else if (!memcmp(r, "maxp", 4)) maxp_off = off, hm = true;
-  }
-  if (!hg || !hl || !hh || !hm || head_off + 54 > n || maxp_off + 6 > n) return MIB_E_INVALID_ARG;
-  const int long_loca = (int16_t)hbe16(ttf + head_off + 50) != 0 ? 1 : 0;
-  const uint32_t ng = hbe16(ttf + maxp_off + 4);
+  DirEntry t[kMaxp + 1];
+  if (!scan_directory(ttf, n, kMaxp + 1, t)) return MIB_E_INVALID_ARG;
+  for (const DirEntry &e : t)
+    if (!e.have) return MIB_E_INVALID_ARG;
+  if (t[kHead].off + 54 > n || t[kMaxp].off + 6 > n) return MIB_E_INVALID_ARG;
+  const uint64_t glyf_len = t[kGlyf].len, loca_len = t[kLoca].len;
+  const int long_loca = (int16_t)hbe16(ttf + t[kHead].off + 50) != 0 ? 1 : 0;
+  const uint32_t ng = hbe16(ttf + t[kMaxp].off + 4);
   if ((uint64_t)(ng + 1) * (long_loca ? 4 : 2) > loca_len || ng == 0) return MIB_E_INVALID_ARG;
-  mib_default_lock(1);
-  mib_ctx *c = mib_default_ctx();
-  if (!c) {
-    mib_default_lock(0);
-    return MIB_E_NO_DEVICE;
-  }
-  hipSetDevice(mib_ctx_device_of(c));
-  hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
-  int rc = 0;
-  {
-    DevMem m;
-    Timer tm{c, st, false, {}};
-    do {
-      uint8_t *d_font = m.take<uint8_t>(glyf_len + loca_len);
-      if (!d_font) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      hipMemcpyAsync(d_font, ttf + glyf_off, glyf_len, hipMemcpyHostToDevice, st);
-      hipMemcpyAsync(d_font + glyf_len, ttf + loca_off, loca_len, hipMemcpyHostToDevice, st);
-      GlyfSized z;
-      if ((rc = mib::woff2dev::transform_glyf_size(st, tm, m, GlyfIn{d_font, (uint32_t)glyf_len, d_font + glyf_len, ng, (uint32_t)long_loca}, &z)))
-        break;
-      uint8_t *d_out = m.take<uint8_t>((size_t)z.total);
-      if (!d_out) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      mib::woff2dev::transform_glyf_write(st, tm, z, d_out);
-      rc = download(st, d_out, z.total, out);
-    } while (0);
-    hipStreamSynchronize(st);   // nothing of this call is in flight when its buffers go
-  }
-  mib_default_lock(0);
-  return rc;
+  Call use(false);   // (the transform wrappers report no kernel times)
+  if (!use.c) return MIB_E_NO_DEVICE;
+  uint8_t *d_font = use.m.take<uint8_t>(glyf_len + loca_len);
+  if (!d_font) return use.rc = MIB_E_OUT_OF_MEMORY;
+  hipMemcpyAsync(d_font, ttf + t[kGlyf].off, glyf_len, hipMemcpyHostToDevice, use.st);
+  hipMemcpyAsync(d_font + glyf_len, ttf + t[kLoca].off, loca_len, hipMemcpyHostToDevice, use.st);
+  GlyfSized z;
+  const GlyfIn in{d_font, (uint32_t)glyf_len, d_font + glyf_len, ng, (uint32_t)long_loca};
+  if ((use.rc = mib::woff2dev::transform_glyf_size(use.st, use.tm, use.m, in, &z))) return use.rc;
+  uint8_t *d_out = use.m.take<uint8_t>((size_t)z.total);
+  if (!d_out) return use.rc = MIB_E_OUT_OF_MEMORY;
+  mib::woff2dev::transform_glyf_write(use.st, use.tm, z, d_out);
+  return use.rc = use.fetch(d_out, (size_t)z.total, out);
 }
 
 // WOFF2 hmtx transform (fontTools WOFF2HmtxTable.transform).  Returns 0 with out->size = 0
@@ -641,65 +617,30 @@ extern "C" int mib_woff2_transform_hmtx(const uint8_t *ttf, size_t n, mib_buf *o
   if (!out || (!ttf && n)) return MIB_E_INVALID_ARG;
   out->data = nullptr;
   out->size = 0;
-  if (n < 12) return MIB_E_INVALID_ARG;
-  const uint32_t ntab = hbe16(ttf + 4);
-  if (12 + 16ull * ntab > n) return MIB_E_INVALID_ARG;
-  uint64_t off[6] = {0, 0, 0, 0, 0, 0}, len[6] = {0, 0, 0, 0, 0, 0};
-  bool have[6] = {false, false, false, false, false, false};
-  static const char *kTags[6] = {"glyf", "loca", "head", "maxp", "hhea", "hmtx"};
-  for (uint32_t i = 0; i < ntab; i++) {
-    const uint8_t *r = ttf + 12 + 16 * i;
-    const uint32_t o = hbe32(r + 8), l = hbe32(r + 12);
-    if ((uint64_t)o + l > n) return MIB_E_INVALID_ARG;
-    for (int t = 0; t < 6; t++)
-      if (!memcmp(r, kTags[t], 4)) off[t] = o, len[t] = l, have[t] = true;
-  }
-  for (int t = 0; t < 6; t++)
-    if (!have[t]) return MIB_E_INVALID_ARG;
-  if (len[2] < 54 || len[3] < 6 || len[4] < 36) return MIB_E_INVALID_ARG;
-  const int long_loca = (int16_t)hbe16(ttf + off[2] + 50) != 0 ? 1 : 0;
-  const uint32_t ng = hbe16(ttf + off[3] + 4), nhm = hbe16(ttf + off[4] + 34);
-  if (ng == 0 || nhm == 0 || nhm > ng || (uint64_t)(ng + 1) * (long_loca ? 4 : 2) > len[1] ||
-      4ull * nhm + 2ull * (ng - nhm) > len[5])
+  DirEntry t[kTags];
+  if (!scan_directory(ttf, n, kTags, t)) return MIB_E_INVALID_ARG;
+  for (const DirEntry &e : t)
+    if (!e.have) return MIB_E_INVALID_ARG;
+  if (t[kHead].len < 54 || t[kMaxp].len < 6 || t[kHhea].len < 36) return MIB_E_INVALID_ARG;
+  const int long_loca = (int16_t)hbe16(ttf + t[kHead].off + 50) != 0 ? 1 : 0;
+  const uint32_t ng = hbe16(ttf + t[kMaxp].off + 4), nhm = hbe16(ttf + t[kHhea].off + 34);
+  const uint64_t gl = t[kGlyf].len, ll = t[kLoca].len, hl = t[kHmtx].len;
+  if (ng == 0 || nhm == 0 || nhm > ng || (uint64_t)(ng + 1) * (long_loca ? 4 : 2) > ll || 4ull * nhm + 2ull * (ng - nhm) > hl)
     return MIB_E_INVALID_ARG;
-  mib_default_lock(1);
-  mib_ctx *c = mib_default_ctx();
-  if (!c) {
-    mib_default_lock(0);
-    return MIB_E_NO_DEVICE;
-  }
-  hipSetDevice(mib_ctx_device_of(c));
-  hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
-  int rc = 0;
-  {
-    DevMem m;
-    Timer tm{c, st, false, {}};
-    do {
-      const uint64_t gl = len[0], ll = len[1], hl = len[5];
-      uint8_t *d_font = m.take<uint8_t>(gl + ll + hl);
-      if (!d_font) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      hipMemcpyAsync(d_font, ttf + off[0], gl, hipMemcpyHostToDevice, st);
-      hipMemcpyAsync(d_font + gl, ttf + off[1], ll, hipMemcpyHostToDevice, st);
-      hipMemcpyAsync(d_font + gl + ll, ttf + off[5], hl, hipMemcpyHostToDevice, st);
-      HmtxSized z;
-      if ((rc = mib::woff2dev::transform_hmtx_size(st, tm, m, GlyfIn{d_font, (uint32_t)gl, d_font + gl, ng, (uint32_t)long_loca},
-                                                   d_font + gl + ll, nhm, &z)))
-        break;
-      if (!z.total) break;   // both arrays needed: no transform
-      uint8_t *d_out = m.take<uint8_t>((size_t)z.total);
-      if (!d_out) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      mib::woff2dev::transform_hmtx_write(st, tm, z, d_out);
-      rc = download(st, d_out, z.total, out);
-    } while (0);
-    hipStreamSynchronize(st);
-  }
-  mib_default_lock(0);
-  return rc;
+  Call use(false);   // (the transform wrappers report no kernel times)
+  if (!use.c) return MIB_E_NO_DEVICE;
+  uint8_t *d_font = use.m.take<uint8_t>(gl + ll + hl);
+  if (!d_font) return use.rc = MIB_E_OUT_OF_MEMORY;
+  hipMemcpyAsync(d_font, ttf + t[kGlyf].off, gl, hipMemcpyHostToDevice, use.st);
+  hipMemcpyAsync(d_font + gl, ttf + t[kLoca].off, ll, hipMemcpyHostToDevice, use.st);
+  hipMemcpyAsync(d_font + gl + ll, ttf + t[kHmtx].off, hl, hipMemcpyHostToDevice, use.st);
+  HmtxSized z;
+  const GlyfIn in{d_font, (uint32_t)gl, d_font + gl, ng, (uint32_t)long_loca};
+  if ((use.rc = mib::woff2dev::transform_hmtx_size(use.st, use.tm, use.m, in, d_font + gl + ll, nhm, &z))) return use.rc;
+  if (!z.total) return 0;   // both arrays needed: no transform
+  uint8_t *d_out = use.m.take<uint8_t>((size_t)z.total);
+  if (!d_out) return use.rc = MIB_E_OUT_OF_MEMORY;
+  mib::woff2dev::transform_hmtx_write(use.st, use.tm, z, d_out);
+  return use.rc = use.fetch(d_out, (size_t)z.total, out);
 }
 

@@ -1,6 +1,6 @@
 // What the WOFF2 host entry points (woff2.hip, woff2_inv.hip, woff2_file.hip, woff2_write.hip)
-// share: a call's device buffers, its per-kernel timer, and the transform and reconstruct cores
-// that work on device memory.
+// share: a call's device buffers, its per-kernel timer, the scope every entry point runs in on
+// the default context (Call), and the transform and reconstruct cores that work on device memory.
 #ifndef MIB_WOFF2_DEV_H_
 #define MIB_WOFF2_DEV_H_
 #include <hip/hip_runtime.h>
@@ -66,24 +66,64 @@ struct DevMem {
   }
 };
 
-// The reconstruct entry points' work between upload and download.  The caller holds the
-// default context's lock, has set its device, and owns the DevMems and `tm`.
-// Return codes as the entry points'; on 0 the stream has been synchronised.
-//   glyf: the transformed table's n bytes at d_t, `hdr` a host copy of its first 36
-//         (woff2_inv.h parse_header has to have accepted hdr, n).  loca follows glyf in memory.
-//         The results live in `keep`, everything else in `m`: once the stream has been
-//         synchronised after the call, `m` may go before the results are used (the two may be
-//         one DevMem).
+inline void drop(mib_buf *b) {   // a result the call does not return after all
+  if (b->data) mib_buf_free(b);
+  b->data = nullptr;
+  b->size = 0;
+}
+
+// One call of an entry point on the default context: the context's lock, its device set, its
+// stream, a timer and the call's buffers.  An entry point that holds one leaves with
+// `return use.rc = <code>`: on a non-zero rc the destructor synchronises the stream, so that
+// nothing of the call is in flight when its buffers go, and the timer's entries count only where
+// the entry point said `timed`.  After the destructor the members die in reverse order: the
+// buffers, and last the lock.
+struct Call {
+  struct Lock {   // (recursive: the decode and encode calls on this context run inside it)
+    Lock() { mib_default_lock(1); }
+    ~Lock() { mib_default_lock(0); }
+  } lock;
+  mib_ctx *c;   // null: no device
+  hipStream_t st;
+  Timer tm;     // on where the entry point times its kernels and the context profiles
+  DevMem m;
+  int rc = 0;
+  bool timed = false;
+  explicit Call(bool timing)
+      : c(mib_default_ctx()), st(c ? (hipStream_t)mib_ctx_stream_of(c) : nullptr),
+        tm{c, st, timing && c && mib_ctx_profiling(c) == 1, {}} {
+    if (c) hipSetDevice(mib_ctx_device_of(c));
+  }
+  Call(const Call &) = delete;
+  ~Call() {
+    if (rc && c) hipStreamSynchronize(st);
+    tm.collect(timed);
+  }
+  // n bytes of device memory into a fresh mib_buf, synchronised; *out is empty on failure
+  int fetch(const uint8_t *d, size_t n, mib_buf *out) {
+    out->size = 0;
+    if (!(out->data = mib_buf_alloc(n))) return MIB_E_OUT_OF_MEMORY;
+    out->size = n;
+    hipMemcpyAsync(out->data, d, n, hipMemcpyDeviceToHost, st);
+    if (hipStreamSynchronize(st) == hipSuccess) return 0;
+    drop(out);
+    return MIB_E_NO_DEVICE;
+  }
+};
+
+// The glyf reconstruct's work between upload and download.  The caller holds the default
+// context's lock, has set its device, and owns the DevMems and `tm`.
+// Return codes as the entry point's; on 0 the stream has been synchronised.
+//   the transformed table's n bytes at d_t, `hdr` a host copy of its first 36 (woff2_inv.h
+//   parse_header has to have accepted hdr, n).  loca follows glyf in memory.  The results live
+//   in `keep`, everything else in `m`: once the stream has been synchronised after the call, `m`
+//   may go before the results are used (the two may be one DevMem).
 int reconstruct_glyf_device(hipStream_t st, Timer &tm, DevMem &m, DevMem &keep, const uint8_t *hdr, const uint8_t *d_t,
                             size_t n, uint8_t **d_glyf, size_t *glyf_b, uint8_t **d_loca, size_t *loca_b);
-//   hmtx: the transformed table's n >= 1 bytes at d_t; its flags and size are checked on the
-//         device.  The caller has checked num_glyphs, num_hmetrics and loca_n (hmtx_shape_ok).
-int reconstruct_hmtx_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *d_t, size_t n, const uint8_t *d_glyf,
-                            size_t glyf_n, const uint8_t *d_loca, uint32_t long_loca, uint32_t num_glyphs,
-                            uint32_t num_hmetrics, uint8_t **d_out, size_t *out_b);
 
-// One font of the hmtx launch (blockIdx.y): what reconstruct_hmtx_device takes, all on the device;
-// out has 4 * nhm + 2 * (ng - nhm) bytes.
+// One font of the hmtx launch (blockIdx.y), all on the device: the transformed table's n >= 1
+// bytes at t (its flags and size are checked on the device), the font's glyf and loca, and out of
+// 4 * nhm + 2 * (ng - nhm) bytes.  The caller has checked ng, nhm and loca's size (hmtx_shape_ok).
 struct HmtxFont {
   const uint8_t *t;
   uint64_t n;

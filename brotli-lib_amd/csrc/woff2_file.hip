@@ -18,6 +18,8 @@
 // font, one hmtx launch, one launch of each assembly kernel over every font, and one
 // synchronisation for the downloads.  Each decode call starts the context's kernel times afresh:
 // after a call of more than one group the times reported are the last group's.
+// mib_woff2_decode is the batch with k = 1, and mib_debug_sfnt_assemble is
+// mib_debug_sfnt_assemble_batch with one font: one code path each.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -151,10 +153,11 @@ __global__ void w2file_peek_kernel(const PeekFont *fonts, uint32_t k, uint8_t *r
 }  // namespace mib
 
 using namespace mib::woff2file;
+using mib::woff2dev::Call;
 using mib::woff2dev::DevMem;
-using mib::woff2dev::Timer;
-
+using mib::woff2dev::drop;
 using mib::woff2dev::HmtxFont;
+using mib::woff2dev::Timer;
 
 extern "C" int mib_ctx_decode_caps(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offsets, size_t k, uint8_t *d_out,
                                    const uint64_t *out_offsets, const uint64_t *out_caps, int64_t *out_sizes, int *status,
@@ -197,38 +200,6 @@ int assemble_device(hipStream_t st, Timer &tm, DevMem &m, const Launch &l, uint8
   return 0;
 }
 
-int download(hipStream_t st, const uint8_t *d_sfnt, size_t n, mib_buf *sfnt) {
-  sfnt->data = mib_buf_alloc(n);
-  if (!sfnt->data) {
-    hipStreamSynchronize(st);
-    return MIB_E_OUT_OF_MEMORY;
-  }
-  sfnt->size = n;
-  hipMemcpyAsync(sfnt->data, d_sfnt, n, hipMemcpyDeviceToHost, st);
-  return hipStreamSynchronize(st) == hipSuccess ? 0 : MIB_E_NO_DEVICE;
-}
-
-struct DefaultCall {   // the default context for one call: lock, device, stream, timer
-  mib_ctx *c;
-  hipStream_t st;
-  DefaultCall() {
-    mib_default_lock(1);
-    c = mib_default_ctx();
-    st = nullptr;
-    if (c) {
-      hipSetDevice(mib_ctx_device_of(c));
-      st = (hipStream_t)mib_ctx_stream_of(c);
-    }
-  }
-  ~DefaultCall() { mib_default_lock(0); }
-};
-
-void drop(mib_buf *b) {
-  if (b->data) mib_buf_free(b);
-  b->data = nullptr;
-  b->size = 0;
-}
-
 // The plan a file of these k tables, all with the null transform, would give, before layout().
 // src_off: the table's place in the font's source bytes (misalign: from a 16-byte boundary on);
 // stream_len: how many those are.
@@ -257,95 +228,6 @@ bool plan_of_tables(uint32_t flavor, const uint32_t *tags, const mib_span *table
     if (pl->t[pl->order[i]].tag == pl->t[pl->order[i - 1]].tag) return false;
   return layout(pl, 0, 0, 0);
 }
-
-}  // namespace
-
-extern "C" int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt) {
-  if (!sfnt) return MIB_E_INVALID_ARG;
-  sfnt->data = nullptr;
-  sfnt->size = 0;
-  Plan pl;
-  if (!parse(woff2, n, &pl)) return MIB_E_INVALID_ARG;   // (before anything is allocated on the device)
-  DefaultCall use;   // (the lock is recursive: mib_ctx_decode below runs on this context inside it)
-  if (!use.c) return MIB_E_NO_DEVICE;
-  hipStream_t st = use.st;
-  int rc = 0;
-  bool timed = false;
-  DevMem m;
-  Launch host;
-  Timer tm{use.c, st, false, {}};
-  do {
-    uint8_t *d_comp = m.take<uint8_t>(pl.comp_len), *d_stream = m.take<uint8_t>((size_t)pl.stream_len);
-    if (!d_comp || !d_stream) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    if (pl.comp_len && hipMemcpyAsync(d_comp, woff2 + pl.comp_off, pl.comp_len, hipMemcpyHostToDevice, st) != hipSuccess) {
-      rc = MIB_E_NO_DEVICE;
-      break;
-    }
-    // the stream has to decode to exactly the directory's total: that is its capacity
-    const uint64_t in_off[2] = {0, pl.comp_len}, out_off[2] = {0, pl.stream_len};
-    int64_t size = 0;
-    int status = 0;
-    rc = mib_ctx_decode(use.c, d_comp, in_off, 1, d_stream, out_off, &size, &status, st);
-    if (rc == 0 || rc == MIB_E_NEED_SPACE) rc = status;
-    if (rc == MIB_E_NEED_SPACE || (rc == 0 && (uint64_t)size != pl.stream_len)) rc = MIB_E_INVALID_ARG;
-    if (rc) break;
-    // (mib_ctx_decode starts the context's kernel times afresh; this call's own follow it)
-    tm.on = mib_ctx_profiling(use.c) == 1;
-    uint8_t *d_glyf = nullptr, *d_loca = nullptr, *d_hmtx = nullptr;
-    size_t glyf_b = 0, loca_b = 0, hmtx_b = 0;
-    if (glyf_transformed(pl)) {
-      const Table &g = pl.t[pl.glyf];
-      uint8_t hdr[mib::woff2inv::kHeaderBytes];
-      if (g.src_len < sizeof(hdr)) {
-        rc = MIB_E_INVALID_ARG;
-        break;
-      }
-      if (hipMemcpyAsync(hdr, d_stream + g.src_off, sizeof(hdr), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) {
-        rc = MIB_E_NO_DEVICE;
-        break;
-      }
-      if ((rc = mib::woff2dev::reconstruct_glyf_device(st, tm, m, m, hdr, d_stream + g.src_off, g.src_len, &d_glyf, &glyf_b,
-                                                       &d_loca, &loca_b)))
-        break;
-      if (hmtx_transformed(pl)) {
-        const Table &h = pl.t[pl.hmtx];
-        uint8_t nhm_be[2];
-        if (hipMemcpyAsync(nhm_be, d_stream + pl.t[pl.hhea].src_off + 34, 2, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-          rc = MIB_E_NO_DEVICE;
-          break;
-        }
-        const uint32_t ng = ((uint32_t)hdr[4] << 8) | hdr[5], nhm = ((uint32_t)nhm_be[0] << 8) | nhm_be[1];
-        uint32_t long_loca = 0;
-        if (!mib::woff2inv::hmtx_shape_ok(h.src_len, glyf_b, loca_b, ng, nhm, &long_loca)) {
-          rc = MIB_E_INVALID_ARG;
-          break;
-        }
-        if ((rc = mib::woff2dev::reconstruct_hmtx_device(st, tm, m, d_stream + h.src_off, h.src_len, d_glyf, glyf_b, d_loca,
-                                                         long_loca, ng, nhm, &d_hmtx, &hmtx_b)))
-          break;
-      }
-    }
-    if (!layout(&pl, glyf_b, loca_b, hmtx_b) || !add_font(&host, pl, FontSrc{d_stream, d_glyf, d_loca, d_hmtx})) {
-      rc = MIB_E_INVALID_ARG;
-      break;
-    }
-    uint8_t *d_sfnt = nullptr;
-    if ((rc = assemble_device(st, tm, m, host, &d_sfnt))) break;
-    if ((rc = download(st, d_sfnt, (size_t)pl.sfnt_len, sfnt))) break;
-    timed = true;
-  } while (0);
-  if (rc) hipStreamSynchronize(st);   // nothing of this call is in flight when its buffers go
-  tm.collect(timed);
-  if (rc) drop(sfnt);
-  return rc;
-}
-
-namespace {
 
 struct BatchFont {   // a file of the group whose stream decoded
   size_t slot;       // in the call's arrays
@@ -563,71 +445,37 @@ extern "C" int mib_woff2_decode_batch(const mib_span *files, size_t k, mib_buf *
     lens.push_back(plans[i].stream_len);
   }
   if (parsed.empty()) return 0;
-  DefaultCall use;   // (the lock is recursive: the decode below runs on this context inside it)
+  Call use(false);   // (every group has its own timer and buffers)
   if (!use.c) return MIB_E_NO_DEVICE;
   g_batch_ms[0] = 0;
-  int rc = 0;
   for (const Group &g : make_groups(lens, g_group_bytes))
-    if ((rc = decode_group(use.c, use.st, files, plans, &parsed[g.first], g.count, sfnt, status))) break;
-  if (rc)
+    if ((use.rc = decode_group(use.c, use.st, files, plans, &parsed[g.first], g.count, sfnt, status))) break;
+  if (use.rc)
     for (size_t i = 0; i < k; i++) drop(&sfnt[i]);
   g_batch_ms[1] = ms_since(call0);
-  return rc;
+  return use.rc;
+}
+
+extern "C" int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt) {
+  if (!sfnt) return MIB_E_INVALID_ARG;
+  sfnt->data = nullptr;
+  sfnt->size = 0;
+  if (!woff2 && n) return MIB_E_INVALID_ARG;
+  const mib_span one{woff2, n};
+  int status = 0;
+  const int rc = mib_woff2_decode_batch(&one, 1, sfnt, &status);
+  return rc ? rc : status;
 }
 
 extern "C" void mib_force_woff2_group_bytes(uint64_t bytes) { g_group_bytes = bytes; }
 uint64_t mib::woff2file::forced_group_bytes() { return g_group_bytes; }   // (the writer's groups: woff2_write.hip)
 
-// diagnostic (DESIGN.md's measurements): host wall time of the last mib_woff2_decode_batch that
-// reached the device -- its per-font glyf reconstruct loops, and the whole call
+// diagnostic (DESIGN.md's measurements): host wall time of the last mib_woff2_decode_batch or
+// mib_woff2_decode (the batch with k = 1) that reached the device -- its per-font glyf
+// reconstruct loops, and the whole call
 extern "C" void mib_woff2_batch_last_ms(double out[2]) {
   out[0] = g_batch_ms[0];
   out[1] = g_batch_ms[1];
-}
-
-extern "C" int mib_debug_sfnt_assemble(uint32_t flavor, const uint32_t *tags, const mib_span *tables,
-                                       const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt) {
-  if (!sfnt) return MIB_E_INVALID_ARG;
-  sfnt->data = nullptr;
-  sfnt->size = 0;
-  if (k == 0 || k > 65535 || !tags || !tables) return MIB_E_INVALID_ARG;
-  Plan pl;
-  if (!plan_of_tables(flavor, tags, tables, d_src_misalign, k, &pl)) return MIB_E_INVALID_ARG;
-  DefaultCall use;
-  if (!use.c) return MIB_E_NO_DEVICE;
-  hipStream_t st = use.st;
-  int rc = 0;
-  bool timed = false;
-  DevMem m;
-  Launch host;
-  Timer tm{use.c, st, mib_ctx_profiling(use.c) == 1, {}};
-  do {
-    uint8_t *d_src = m.take<uint8_t>((size_t)pl.stream_len);
-    if (!d_src) {
-      rc = MIB_E_OUT_OF_MEMORY;
-      break;
-    }
-    bool ok = true;
-    for (size_t i = 0; i < k; i++)
-      if (tables[i].size)
-        ok = ok && hipMemcpyAsync(d_src + pl.t[i].src_off, tables[i].data, tables[i].size, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok) {
-      rc = MIB_E_NO_DEVICE;
-      break;
-    }
-    if (!add_font(&host, pl, FontSrc{d_src, nullptr, nullptr, nullptr})) {
-      rc = MIB_E_INVALID_ARG;
-      break;
-    }
-    uint8_t *d_sfnt = nullptr;
-    if ((rc = assemble_device(st, tm, m, host, &d_sfnt))) break;
-    if ((rc = download(st, d_sfnt, (size_t)pl.sfnt_len, sfnt))) break;
-    timed = true;
-  } while (0);
-  if (rc) hipStreamSynchronize(st);
-  tm.collect(timed);
-  if (rc) drop(sfnt);
-  return rc;
 }
 
 extern "C" int mib_debug_sfnt_assemble_batch(const uint32_t *flavors, const uint32_t *counts, const uint32_t *tags,
@@ -655,45 +503,38 @@ extern "C" int mib_debug_sfnt_assemble_batch(const uint32_t *flavors, const uint
       if (tables[first + i].size) memcpy(stage.data() + base[f] + plans[f].t[i].src_off, tables[first + i].data, tables[first + i].size);
     first += counts[f];
   }
-  DefaultCall use;
+  Launch host;   // (declared before the scope: the launches read it until the stream is synchronised)
+  Call use(true);
   if (!use.c) return MIB_E_NO_DEVICE;
-  hipStream_t st = use.st;
-  int rc = 0;
-  bool timed = false;
-  DevMem m;
-  Launch host;
-  Timer tm{use.c, st, mib_ctx_profiling(use.c) == 1, {}};
-  do {
-    uint8_t *d_src = m.take<uint8_t>(total);
-    if (!d_src) {
-      rc = MIB_E_OUT_OF_MEMORY;
+  uint8_t *d_src = use.m.take<uint8_t>(total), *d_out = nullptr;
+  if (!d_src) return use.rc = MIB_E_OUT_OF_MEMORY;
+  if (total && hipMemcpyAsync(d_src, stage.data(), total, hipMemcpyHostToDevice, use.st) != hipSuccess)
+    return use.rc = MIB_E_NO_DEVICE;
+  for (size_t f = 0; f < k; f++)
+    if (!add_font(&host, plans[f], FontSrc{d_src + base[f], nullptr, nullptr, nullptr})) return use.rc = MIB_E_INVALID_ARG;
+  if ((use.rc = assemble_device(use.st, use.tm, use.m, host, &d_out))) return use.rc;
+  for (size_t f = 0; f < k; f++) {   // every font's download, then one synchronisation
+    sfnt[f].data = mib_buf_alloc((size_t)plans[f].sfnt_len);
+    if (!sfnt[f].data) {
+      use.rc = MIB_E_OUT_OF_MEMORY;
       break;
     }
-    if (total && hipMemcpyAsync(d_src, stage.data(), total, hipMemcpyHostToDevice, st) != hipSuccess) {
-      rc = MIB_E_NO_DEVICE;
-      break;
-    }
-    for (size_t f = 0; f < k && !rc; f++)
-      if (!add_font(&host, plans[f], FontSrc{d_src + base[f], nullptr, nullptr, nullptr})) rc = MIB_E_INVALID_ARG;
-    if (rc) break;
-    uint8_t *d_out = nullptr;
-    if ((rc = assemble_device(st, tm, m, host, &d_out))) break;
-    for (size_t f = 0; f < k; f++) {
-      sfnt[f].data = mib_buf_alloc((size_t)plans[f].sfnt_len);
-      if (!sfnt[f].data) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      sfnt[f].size = (size_t)plans[f].sfnt_len;
-      hipMemcpyAsync(sfnt[f].data, d_out + host.fonts[f].out_base, sfnt[f].size, hipMemcpyDeviceToHost, st);
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = MIB_E_NO_DEVICE;
-    if (rc) break;
-    timed = true;
-  } while (0);
-  if (rc) hipStreamSynchronize(st);
-  tm.collect(timed);
-  if (rc)
+    sfnt[f].size = (size_t)plans[f].sfnt_len;
+    hipMemcpyAsync(sfnt[f].data, d_out + host.fonts[f].out_base, sfnt[f].size, hipMemcpyDeviceToHost, use.st);
+  }
+  if (hipStreamSynchronize(use.st) != hipSuccess && !use.rc) use.rc = MIB_E_NO_DEVICE;
+  if (use.rc)
     for (size_t f = 0; f < k; f++) drop(&sfnt[f]);
-  return rc;
+  use.timed = use.rc == 0;
+  return use.rc;
+}
+
+extern "C" int mib_debug_sfnt_assemble(uint32_t flavor, const uint32_t *tags, const mib_span *tables,
+                                       const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt) {
+  if (!sfnt) return MIB_E_INVALID_ARG;
+  sfnt->data = nullptr;
+  sfnt->size = 0;
+  if (k == 0 || k > 65535 || !tags || !tables) return MIB_E_INVALID_ARG;   // (k counts tables here: none is no font)
+  const uint32_t count = (uint32_t)k;
+  return mib_debug_sfnt_assemble_batch(&flavor, &count, tags, tables, d_src_misalign, 1, sfnt);
 }

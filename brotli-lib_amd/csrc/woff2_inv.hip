@@ -357,6 +357,7 @@ __global__ void inv_hmtx_kernel(const mib::woff2dev::HmtxFont *fonts, uint32_t k
 }  // namespace mib
 
 using namespace mib::woff2inv;
+using mib::woff2dev::Call;
 using mib::woff2dev::DevMem;
 using mib::woff2dev::HmtxFont;
 using mib::woff2dev::Timer;
@@ -487,55 +488,33 @@ extern "C" int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_bu
   if (!tglyf) return MIB_E_INVALID_ARG;
   View hv;
   if (!parse_header(tglyf, n, tglyf, &hv)) return MIB_E_INVALID_ARG;
-  mib_default_lock(1);
-  mib_ctx *c = mib_default_ctx();
-  if (!c) {
-    mib_default_lock(0);
-    return MIB_E_NO_DEVICE;
+  Call use(true);
+  if (!use.c) return MIB_E_NO_DEVICE;
+  uint8_t *d_t = use.m.take<uint8_t>(n), *d_glyf = nullptr, *d_loca = nullptr;
+  size_t glyf_b = 0, loca_b = 0;
+  if (!d_t) return use.rc = MIB_E_OUT_OF_MEMORY;
+  hipMemcpyAsync(d_t, tglyf, n, hipMemcpyHostToDevice, use.st);
+  if ((use.rc = mib::woff2dev::reconstruct_glyf_device(use.st, use.tm, use.m, use.m, tglyf, d_t, n, &d_glyf, &glyf_b, &d_loca,
+                                                       &loca_b)))
+    return use.rc;
+  // two results, one synchronisation (Call::fetch would take one each)
+  glyf->data = mib_buf_alloc(glyf_b);
+  loca->data = mib_buf_alloc(loca_b);
+  if (glyf->data && loca->data) {
+    glyf->size = glyf_b;
+    loca->size = loca_b;
+    hipMemcpyAsync(glyf->data, d_glyf, glyf_b, hipMemcpyDeviceToHost, use.st);
+    hipMemcpyAsync(loca->data, d_loca, loca_b, hipMemcpyDeviceToHost, use.st);
+    use.rc = hipStreamSynchronize(use.st) == hipSuccess ? 0 : MIB_E_NO_DEVICE;
+  } else {
+    use.rc = MIB_E_OUT_OF_MEMORY;
   }
-  hipSetDevice(mib_ctx_device_of(c));
-  hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
-  Timer tm{c, st, mib_ctx_profiling(c) == 1, {}};
-  int rc = 0;
-  bool timed = false;
-  {
-    DevMem m;
-    do {
-      uint8_t *d_t = m.take<uint8_t>(n), *d_glyf = nullptr, *d_loca = nullptr;
-      size_t glyf_b = 0, loca_b = 0;
-      if (!d_t) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      hipMemcpyAsync(d_t, tglyf, n, hipMemcpyHostToDevice, st);
-      if ((rc = mib::woff2dev::reconstruct_glyf_device(st, tm, m, m, tglyf, d_t, n, &d_glyf, &glyf_b, &d_loca, &loca_b))) break;
-      glyf->data = mib_buf_alloc(glyf_b);
-      loca->data = mib_buf_alloc(loca_b);
-      if (!glyf->data || !loca->data) {
-        hipStreamSynchronize(st);
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      glyf->size = glyf_b;
-      loca->size = loca_b;
-      hipMemcpyAsync(glyf->data, d_glyf, glyf_b, hipMemcpyDeviceToHost, st);
-      hipMemcpyAsync(loca->data, d_loca, loca_b, hipMemcpyDeviceToHost, st);
-      if (hipStreamSynchronize(st) != hipSuccess) {
-        rc = MIB_E_NO_DEVICE;
-        break;
-      }
-      timed = true;
-    } while (0);
-    tm.collect(timed);
+  if (use.rc) {
+    mib::woff2dev::drop(glyf);
+    mib::woff2dev::drop(loca);
   }
-  if (rc) {
-    if (glyf->data) mib_buf_free(glyf);
-    if (loca->data) mib_buf_free(loca);
-    glyf->data = loca->data = nullptr;
-    glyf->size = loca->size = 0;
-  }
-  mib_default_lock(0);
-  return rc;
+  use.timed = use.rc == 0;
+  return use.rc;
 }
 
 void mib::woff2dev::launch_hmtx(hipStream_t st, Timer &tm, const HmtxFont *d_fonts, size_t k, uint32_t most_ng, int *d_bad) {
@@ -545,28 +524,8 @@ void mib::woff2dev::launch_hmtx(hipStream_t st, Timer &tm, const HmtxFont *d_fon
   tm.stop();
 }
 
-int mib::woff2dev::reconstruct_hmtx_device(hipStream_t st, Timer &tm, DevMem &m, const uint8_t *d_t, size_t n,
-                                           const uint8_t *d_glyf, size_t glyf_n, const uint8_t *d_loca, uint32_t long_loca,
-                                           uint32_t ng, uint32_t nhm, uint8_t **d_out_p, size_t *out_b) {
-  const size_t total = 4 * (size_t)nhm + 2 * (size_t)(ng - nhm);
-  uint8_t *d_out = m.take<uint8_t>(total);
-  int *d_bad = m.take<int>(1);
-  HmtxFont *d_font = m.take<HmtxFont>(1);
-  if (!d_out || !d_bad || !d_font) return MIB_E_OUT_OF_MEMORY;
-  const HmtxFont font{d_t, (uint64_t)n, d_glyf, d_loca, d_out, (uint32_t)glyf_n, long_loca, ng, nhm};
-  hipMemsetAsync(d_bad, 0, 4, st);
-  hipMemcpyAsync(d_font, &font, sizeof(font), hipMemcpyHostToDevice, st);   // (synchronised below)
-  launch_hmtx(st, tm, d_font, 1, ng, d_bad);
-  int bad = 0;
-  hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st);
-  if (hipStreamSynchronize(st) != hipSuccess) return MIB_E_NO_DEVICE;
-  // flags that do not fit the size; a loca entry that does not fit the glyf table
-  if (bad) return MIB_E_INVALID_ARG;
-  *d_out_p = d_out;
-  *out_b = total;
-  return 0;
-}
-
+// The launch over one font: the table's flags and size are checked on the device, as in the file
+// decoder's launch over many (woff2_file.hip).
 extern "C" int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const uint8_t *glyf, size_t glyf_n,
                                           const uint8_t *loca, size_t loca_n, uint32_t num_glyphs,
                                           uint32_t num_hmetrics, mib_buf *out) {
@@ -577,54 +536,29 @@ extern "C" int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const 
   if (!loca || (!glyf && glyf_n) ||
       !hmtx_args_ok(thmtx, n, glyf_n, loca_n, num_glyphs, num_hmetrics, &long_loca))
     return MIB_E_INVALID_ARG;
-  mib_default_lock(1);
-  mib_ctx *c = mib_default_ctx();
-  if (!c) {
-    mib_default_lock(0);
-    return MIB_E_NO_DEVICE;
+  Call use(true);
+  if (!use.c) return MIB_E_NO_DEVICE;
+  const size_t total = 4 * (size_t)num_hmetrics + 2 * (size_t)(num_glyphs - num_hmetrics);
+  uint8_t *d_in = use.m.take<uint8_t>(n + glyf_n + loca_n), *d_out = use.m.take<uint8_t>(total);
+  int *d_bad = use.m.take<int>(1);
+  HmtxFont *d_font = use.m.take<HmtxFont>(1);
+  if (!d_in || !d_out || !d_bad || !d_font) return use.rc = MIB_E_OUT_OF_MEMORY;
+  hipMemcpyAsync(d_in, thmtx, n, hipMemcpyHostToDevice, use.st);
+  if (glyf_n) hipMemcpyAsync(d_in + n, glyf, glyf_n, hipMemcpyHostToDevice, use.st);
+  hipMemcpyAsync(d_in + n + glyf_n, loca, loca_n, hipMemcpyHostToDevice, use.st);
+  const HmtxFont font{d_in, (uint64_t)n, d_in + n, d_in + n + glyf_n, d_out, (uint32_t)glyf_n, long_loca, num_glyphs, num_hmetrics};
+  hipMemsetAsync(d_bad, 0, 4, use.st);
+  hipMemcpyAsync(d_font, &font, sizeof(font), hipMemcpyHostToDevice, use.st);   // (synchronised below)
+  mib::woff2dev::launch_hmtx(use.st, use.tm, d_font, 1, num_glyphs, d_bad);
+  int bad = 0;
+  hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, use.st);
+  if (hipStreamSynchronize(use.st) != hipSuccess) return use.rc = MIB_E_NO_DEVICE;
+  // flags that do not fit the size; a loca entry that does not fit the glyf table
+  if (bad) {
+    use.timed = true;   // (the kernel ran)
+    return use.rc = MIB_E_INVALID_ARG;
   }
-  hipSetDevice(mib_ctx_device_of(c));
-  hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
-  Timer tm{c, st, mib_ctx_profiling(c) == 1, {}};
-  int rc = 0;
-  bool timed = false;
-  {
-    DevMem m;
-    do {
-      uint8_t *d_in = m.take<uint8_t>(n + glyf_n + loca_n), *d_out = nullptr;
-      size_t total = 0;
-      if (!d_in) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      hipMemcpyAsync(d_in, thmtx, n, hipMemcpyHostToDevice, st);
-      if (glyf_n) hipMemcpyAsync(d_in + n, glyf, glyf_n, hipMemcpyHostToDevice, st);
-      hipMemcpyAsync(d_in + n + glyf_n, loca, loca_n, hipMemcpyHostToDevice, st);
-      if ((rc = mib::woff2dev::reconstruct_hmtx_device(st, tm, m, d_in, n, d_in + n, glyf_n, d_in + n + glyf_n, long_loca,
-                                                       num_glyphs, num_hmetrics, &d_out, &total))) {
-        timed = rc == MIB_E_INVALID_ARG;   // (the kernel ran)
-        break;
-      }
-      out->data = mib_buf_alloc(total);
-      if (!out->data) {
-        rc = MIB_E_OUT_OF_MEMORY;
-        break;
-      }
-      out->size = total;
-      hipMemcpyAsync(out->data, d_out, total, hipMemcpyDeviceToHost, st);
-      if (hipStreamSynchronize(st) != hipSuccess) {
-        rc = MIB_E_NO_DEVICE;
-        break;
-      }
-      timed = true;
-    } while (0);
-    tm.collect(timed);
-  }
-  if (rc && out->data) {
-    mib_buf_free(out);
-    out->data = nullptr;
-    out->size = 0;
-  }
-  mib_default_lock(0);
-  return rc;
+  use.rc = use.fetch(d_out, total, out);
+  use.timed = use.rc == 0;
+  return use.rc;
 }

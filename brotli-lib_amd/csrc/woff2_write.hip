@@ -71,7 +71,9 @@ __global__ __launch_bounds__(kPackThreads) void w2enc_pack_kernel(const PackDesc
 }  // namespace mib
 
 using namespace mib::woff2write;
+using mib::woff2dev::Call;
 using mib::woff2dev::DevMem;
+using mib::woff2dev::drop;
 using mib::woff2dev::GlyfIn;
 using mib::woff2dev::GlyfSized;
 using mib::woff2dev::HmtxSized;
@@ -80,27 +82,6 @@ using mib::woff2dev::Timer;
 extern "C" uint64_t mib_encode_out_bound(uint64_t n);
 
 namespace {
-
-struct DefaultCall {   // the default context for one call: lock, device, stream
-  mib_ctx *c;
-  hipStream_t st;
-  DefaultCall() {
-    mib_default_lock(1);
-    c = mib_default_ctx();
-    st = nullptr;
-    if (c) {
-      hipSetDevice(mib_ctx_device_of(c));
-      st = (hipStream_t)mib_ctx_stream_of(c);
-    }
-  }
-  ~DefaultCall() { mib_default_lock(0); }
-};
-
-void drop(mib_buf *b) {
-  if (b->data) mib_buf_free(b);
-  b->data = nullptr;
-  b->size = 0;
-}
 
 struct GroupFont {   // a font of the group whose plan parsed
   size_t slot;       // in the call's arrays
@@ -298,12 +279,11 @@ int encode_batch(const mib_span *sfnts, size_t k, const mib_woff2_enc_opts *o, m
     lens.push_back(sfnts[i].size);
   }
   if (parsed.empty()) return 0;
-  DefaultCall use;
+  Call use(false);   // (every group has its own timer and buffers)
   if (!use.c) return MIB_E_NO_DEVICE;
-  int rc = 0;
   for (const mib::woff2file::Group &g : mib::woff2file::make_groups(lens, mib::woff2file::forced_group_bytes()))
-    if ((rc = encode_group(use.c, use.st, sfnts, plans, &parsed[g.first], g.count, eo, woff2, status))) break;
-  return rc;
+    if ((use.rc = encode_group(use.c, use.st, sfnts, plans, &parsed[g.first], g.count, eo, woff2, status))) break;
+  return use.rc;
 }
 
 }  // namespace

@@ -763,7 +763,8 @@ def force_woff2_group_bytes(n):
 
 def woff2_batch_last_ms():
     """Diagnostic (measurements): (the per-font glyf reconstruct loops, the whole call) of the last
-    woff2_decode_batch that reached the device, host wall time in ms."""
+    woff2_decode_batch or woff2_decode (which is the batch with one file) that reached the device,
+    host wall time in ms."""
     out = (ctypes.c_double * 2)()
     _L().mib_woff2_batch_last_ms(out)
     return out[0], out[1]

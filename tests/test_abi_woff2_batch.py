@@ -1,7 +1,9 @@
 """CPU-side checks of the batched WOFF2 file decoder's C ABI (include/brotli_amd.h,
 mib_woff2_decode_batch): the symbols are exported and declared, malformed calls are refused, an
 empty batch touches nothing, and a batch made only of files whose container does not parse is
-answered per slot without a device (this file runs without a GPU)."""
+answered per slot without a device; mib_woff2_decode and mib_debug_sfnt_assemble, which are the
+batch forms with one file and one font, keep their own argument contract (this file runs without
+a GPU)."""
 import ctypes
 import os
 import re
@@ -92,6 +94,40 @@ def test_batch_of_unparsable_files_needs_no_device():
     assert lib.mib_woff2_decode_batch(spans, k, outs, st) == 0
     assert list(st) == [wf.MIB_E_INVALID_ARG] * k, [c[0] for c, s in zip(cases, st) if s != wf.MIB_E_INVALID_ARG]
     assert [(o.data, o.size) for o in outs] == [(None, 0)] * k
+
+
+def test_solo_decode_argument_contract_needs_no_device():
+    """mib_woff2_decode is the batch with k = 1: its own argument checks, and a file that does not
+    parse is refused before the device is touched"""
+    lib = _lib()
+    lib.mib_woff2_decode.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    one = ctypes.create_string_buffer(b'wOF2', 4)
+    assert lib.mib_woff2_decode(ctypes.addressof(one), 4, None) == wf.MIB_E_INVALID_ARG
+    out = Buf(0xdead, 99)
+    assert lib.mib_woff2_decode(None, 4, ctypes.byref(out)) == wf.MIB_E_INVALID_ARG
+    assert (out.data, out.size) == (None, 0)
+    for name, file, _, _ in _unparsable():
+        keep = ctypes.create_string_buffer(file, max(len(file), 1))
+        out = Buf(0xdead, 99)
+        assert lib.mib_woff2_decode(ctypes.addressof(keep) if len(file) else None, len(file), ctypes.byref(out)) == \
+            wf.MIB_E_INVALID_ARG, name
+        assert (out.data, out.size) == (None, 0), name
+
+
+def test_solo_assemble_argument_contract():
+    """mib_debug_sfnt_assemble is the batch with one font, but its k counts tables: none is an error"""
+    lib = _lib()
+    lib.mib_debug_sfnt_assemble.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_size_t, ctypes.c_void_p]
+    tag = (ctypes.c_uint32 * 1)(0x636D6170)
+    byte = ctypes.create_string_buffer(b'x', 1)
+    table = (Span * 1)(Span(ctypes.addressof(byte), 1))
+    out = Buf(0xdead, 99)
+    assert lib.mib_debug_sfnt_assemble(0x00010000, tag, table, None, 0, ctypes.byref(out)) == wf.MIB_E_INVALID_ARG
+    assert (out.data, out.size) == (None, 0)
+    out = Buf(0xdead, 99)
+    assert lib.mib_debug_sfnt_assemble(0x00010000, None, table, None, 1, ctypes.byref(out)) == wf.MIB_E_INVALID_ARG
+    assert (out.data, out.size) == (None, 0)
 
 
 def test_python_mirror_surface():

@@ -7,6 +7,7 @@ kernel per group; and the batched assembly kernels alone agree with the Python a
 (tests/_woff2_file.assemble) on the shapes at which a launch over several fonts can go wrong and
 a launch over one cannot."""
 import hashlib
+import json
 import os
 import random
 import shutil
@@ -91,7 +92,13 @@ def _bad_files():
 
 
 def test_bad_files_keep_their_codes_and_leave_the_good_ones_alone():
+    """woff2_decode is the batch with one file, so the codes are pinned: decode_codes.json holds
+    what woff2_decode gave for each of these files while it still was a path of its own"""
     bad = _bad_files()
+    with open(os.path.join(wf.HERE, 'decode_codes.json')) as f:
+        recorded = json.load(f)
+    assert sorted(recorded) == sorted(name for name, _ in bad)
+    assert all(code == wf.MIB_E_INVALID_ARG for name, code in recorded.items() if name != 'flipped-byte')
     files, kind = [], []
     for i, (name, file) in enumerate(bad):
         files.append(file)
@@ -101,8 +108,9 @@ def test_bad_files_keep_their_codes_and_leave_the_good_ones_alone():
     out = brotli_amd.woff2_decode_batch(files)
     assert len(out) == len(files)
     for (name, file), o in zip(bad, out[0::2]):
-        want = _solo(file)
+        want = recorded[name]
         assert isinstance(want, int) and want < 0, name
+        assert _solo(file) == want, name
         assert isinstance(o, brotli_amd.BrotliError) and o.code == want, (name, o, want)
     for g, o in zip(kind[1::2], out[1::2]):
         _is_golden(o, GOLD[g])

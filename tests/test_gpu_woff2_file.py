@@ -117,15 +117,30 @@ def test_profile_names_of_the_new_and_the_old_entry_points():
     name, ttf = next(iter(make_golden.fonts()))
     assert name == 'enc-ttf'
     tglyf = brotli_amd.woff2_transform_glyf(ttf)
+    thmtx = brotli_amd.woff2_transform_hmtx(ttf)
+    glyf, loca = brotli_amd.woff2_reconstruct_glyf(tglyf)
+    ng = int.from_bytes(tglyf[4:6], 'big')
+    nhm = int.from_bytes(wf.sfnt_tables(ttf)[b'hhea'][34:36], 'big')
     data = next(fx[1] for fx in wf.golden_files() if fx[0] == 'enc-ttf-hmtx')
     try:
+        # the transform wrappers run with the timer off: they report nothing
+        brotli_amd.default_profiling(True)
+        assert brotli_amd.woff2_transform_glyf(ttf) == tglyf
+        assert sorted(brotli_amd.default_kernel_times()) == []
+        brotli_amd.default_profiling(True)
+        assert brotli_amd.woff2_transform_hmtx(ttf) == thmtx
+        assert sorted(brotli_amd.default_kernel_times()) == []
         brotli_amd.default_profiling(True)
         brotli_amd.woff2_reconstruct_glyf(tglyf)
         assert sorted(brotli_amd.default_kernel_times()) == W2INV_GLYF_KERNELS
         brotli_amd.default_profiling(True)
+        brotli_amd.woff2_reconstruct_hmtx(thmtx, glyf, loca, ng, nhm)
+        assert {k: v[1] for k, v in brotli_amd.default_kernel_times().items()} == {'w2inv_hmtx': 1}
+        brotli_amd.default_profiling(True)
         brotli_amd.woff2_decode(data)
         times = brotli_amd.default_kernel_times()
         assert times['w2file_assemble'][1] == 1 and times['w2file_directory'][1] == 1
+        assert times['w2file_peek'][1] == 1   # woff2_decode is the batch with one file
         assert any(k.startswith('decode_') for k in times)   # the Brotli stream, on the same context
         assert sorted(k for k in times if k.startswith('w2inv_')) == sorted(W2INV_GLYF_KERNELS + ['w2inv_hmtx'])
     finally:
