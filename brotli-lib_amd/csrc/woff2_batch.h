@@ -15,7 +15,9 @@
 //              descriptor per font.  Every sfnt begins at a 16-byte boundary of the one output
 //              buffer: the assembly lays 16-byte granules over the output, and two fonts must
 //              not share one.  A font's base is 64 bits and the offsets inside a font stay the 32
-//              bits they are in the sfnt, so a group's output may pass 4 GiB.
+//              bits they are in the sfnt, so a group's output may pass 4 GiB.  A collection is
+//              one output file (its TTC) with a DirFont per member: the members share the
+//              file's base and sums, and each has its directory's place in the file (dir_off).
 #ifndef MIB_WOFF2_BATCH_H_
 #define MIB_WOFF2_BATCH_H_
 #include <stddef.h>
@@ -90,21 +92,31 @@ struct AsmDesc {
   uint32_t zero_at;    // head with its checkSumAdjustment: 8 (bytes 8..11 are stored as zero); else kNoZero
   uint32_t sum;        // its slot of the launch's sums
 };
-// One record of a font's directory, in tag order.  `table` counts from the font's first sum.
+// One record of a font's directory, in tag order.  `table` counts from the font's first sum:
+// the file's written tables in the directory's order (a table that several members of a
+// collection list has one sum, and every record that lists it reaches it).
 struct DirRec {
   uint32_t tag, table, dst_off, len;
 };
-// One font of the directory launch.
+// One font of the directory launch: a single font, or a member of a collection -- the members of
+// one collection share out_base (the TTC's place), first_sum, and nothing else.
 struct DirFont {
   uint64_t out_base;
   uint32_t flavor, num, range, selector, shift;
   uint32_t first_rec, first_sum;   // in the launch's records and sums
-  uint32_t adjust_at;              // head's checkSumAdjustment in the font, or kNoZero
+  uint32_t adjust_at;              // head's checkSumAdjustment in the file, or kNoZero (a member: unless
+                                   // it is the last that lists its head)
+  uint32_t dir_off = 0;            // the offset table's place in the file (0: a single font)
+  uint32_t ttc_index = kNoZero;    // a member's place in its collection: it stores its word of the TTC
+                                   // header, member 0 the words before them (and behind, version 2.0)
+  uint32_t ttc_version = 0, ttc_fonts = 0;
 };
 
-// Where a font's tables lie once its stream is decoded and its tables are reconstructed.
+// Where a font's tables lie once its stream is decoded and its tables are reconstructed.  A
+// collection's (and any plan's, by its pairs and hmtx units): glyfs / locas per pair, hmtxs per unit.
 struct FontSrc {
   const uint8_t *stream, *glyf, *loca, *hmtx;
+  const uint8_t *const *glyfs = nullptr, *const *locas = nullptr, *const *hmtxs = nullptr;
 };
 
 struct Launch {
@@ -115,13 +127,60 @@ struct Launch {
   uint64_t most_tiles = 1;  // of any one table (the tile spread of the launch)
 };
 
-// Append a laid-out font.  False (nothing appended) where the launch's table count would leave
-// what one grid dimension holds.
-inline bool add_font(Launch *l, const Plan &pl, const FontSrc &src) {
+// Append a laid-out collection: one output file, a descriptor per written table, a DirFont per
+// member.  False (nothing appended) as add_font.
+inline bool add_collection(Launch *l, const Plan &pl, const FontSrc &src) {
   const uint64_t num = pl.t.size();
-  if ((uint64_t)l->descs.size() + num > 0x7FFFFFFFull) return false;
+  uint64_t written = 0, records = 0;
+  for (uint64_t i = 0; i < num; i++) written += pl.written[i];
+  for (const Member &m : pl.fonts) records += m.order.size();
+  if ((uint64_t)l->descs.size() + written > 0x7FFFFFFFull || (uint64_t)l->recs.size() + records > 0x7FFFFFFFull ||
+      (uint64_t)l->fonts.size() + pl.fonts.size() > 0x7FFFFFFFull)
+    return false;
   const uint64_t base = (l->out_bytes + kFontAlign - 1) & ~(kFontAlign - 1);
   const uint32_t first = (uint32_t)l->descs.size();
+  std::vector<uint32_t> slot(num, 0);   // a written table's place among the file's sums
+  for (uint32_t i = 0; i < num; i++) {
+    if (!pl.written[i]) continue;
+    const Table &t = pl.t[i];
+    const uint8_t *s = t.kind == kGlyf ? src.glyfs[pl.unit[i]] : t.kind == kLoca ? src.locas[pl.unit[i]]
+                       : t.kind == kHmtx ? src.hmtxs[pl.unit[i]] : src.stream + t.src_off;
+    slot[i] = (uint32_t)l->descs.size() - first;
+    l->descs.push_back(AsmDesc{s, base, t.dst_off, t.dst_len, head_zeroed(pl, i) ? 8u : kNoZero, first + slot[i]});
+    const uint64_t tiles = ((uint64_t)t.dst_len + 3 + (t.dst_off & 15) + kAsmTile - 1) / kAsmTile;
+    l->most_tiles = tiles > l->most_tiles ? tiles : l->most_tiles;
+  }
+  for (size_t m = 0; m < pl.fonts.size(); m++) {
+    const Member &mem = pl.fonts[m];
+    DirFont f;
+    f.out_base = base;
+    f.flavor = mem.flavor;
+    f.num = (uint32_t)mem.order.size();
+    search_fields(f.num, &f.range, &f.selector, &f.shift);
+    f.selector &= 0xFFFF;
+    f.first_rec = (uint32_t)l->recs.size();
+    f.first_sum = first;
+    f.adjust_at = member_adjusts(pl, mem) ? pl.t[mem.head].dst_off + 8 : kNoZero;
+    f.dir_off = mem.dir_off;
+    f.ttc_index = (uint32_t)m;
+    f.ttc_version = pl.ttc_version;
+    f.ttc_fonts = (uint32_t)pl.fonts.size();
+    for (uint32_t i : mem.order) l->recs.push_back(DirRec{pl.t[i].tag, slot[i], pl.t[i].dst_off, pl.t[i].dst_len});
+    l->fonts.push_back(f);
+  }
+  l->out_bytes = base + pl.sfnt_len;
+  return true;
+}
+
+// Append a laid-out font (a collection: add_collection).  False (nothing appended) where the
+// launch's table count would leave what one grid dimension holds.
+inline bool add_font(Launch *l, const Plan &pl, const FontSrc &src) {
+  if (pl.ttc_version) return add_collection(l, pl, src);
+  const uint64_t num = pl.t.size();
+  if ((uint64_t)l->descs.size() + num > 0x7FFFFFFFull || (uint64_t)l->recs.size() + num > 0x7FFFFFFFull) return false;
+  const uint64_t base = (l->out_bytes + kFontAlign - 1) & ~(kFontAlign - 1);
+  // (the records run ahead of the tables only behind a collection whose members share tables)
+  const uint32_t first = (uint32_t)l->descs.size(), first_rec = (uint32_t)l->recs.size();
   for (uint32_t i = 0; i < num; i++) {
     const Table &t = pl.t[i];
     const uint8_t *s = t.kind == kGlyf ? src.glyf : t.kind == kLoca ? src.loca : t.kind == kHmtx ? src.hmtx
@@ -140,7 +199,8 @@ inline bool add_font(Launch *l, const Plan &pl, const FontSrc &src) {
   f.num = (uint32_t)num;
   search_fields(f.num, &f.range, &f.selector, &f.shift);
   f.selector &= 0xFFFF;
-  f.first_rec = f.first_sum = first;
+  f.first_rec = first_rec;
+  f.first_sum = first;
   f.adjust_at = head_adjusted(pl) ? pl.t[pl.head].dst_off + 8 : kNoZero;
   l->fonts.push_back(f);
   l->out_bytes = base + pl.sfnt_len;
@@ -162,7 +222,18 @@ inline void host_run(const Launch &l, uint8_t *out) {
     sums[d.sum] = sum_words(dst, padded);
   }
   for (const DirFont &f : l.fonts) {
-    uint8_t *o = out + f.out_base;
+    uint8_t *o = out + f.out_base + f.dir_off;
+    if (f.ttc_index != kNoZero) {
+      uint8_t *h = out + f.out_base;
+      put32(h + 12 + 4 * (size_t)f.ttc_index, f.dir_off);
+      if (f.ttc_index == 0) {
+        put32(h, kFlavorTtc);
+        put32(h + 4, f.ttc_version);
+        put32(h + 8, f.ttc_fonts);
+        if (f.ttc_version == kTtcVersion2)
+          for (int w = 0; w < 3; w++) put32(h + 12 + 4 * ((size_t)f.ttc_fonts + w), 0);
+      }
+    }
     put32(o, f.flavor);
     woff2inv::put16(o + 4, f.num);
     woff2inv::put16(o + 6, f.range);
@@ -179,7 +250,7 @@ inline void host_run(const Launch &l, uint8_t *out) {
       total += sums[f.first_sum + rec.table];
     }
     total += sum_words(o, 12 + 16 * (size_t)f.num);
-    if (f.adjust_at != kNoZero) put32(o + f.adjust_at, kHeadMagic - total);
+    if (f.adjust_at != kNoZero) put32(out + f.out_base + f.adjust_at, kHeadMagic - total);
   }
 }
 

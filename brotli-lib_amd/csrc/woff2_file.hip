@@ -20,6 +20,13 @@
 // after a call of more than one group the times reported are the last group's.
 // mib_woff2_decode is the batch with k = 1, and mib_debug_sfnt_assemble is
 // mib_debug_sfnt_assemble_batch with one font: one code path each.
+//
+// A font collection (flavor ttcf; DESIGN.md 4c "A font collection") is one file of a group like
+// any other and comes out as its TTC: a peek row and a reconstruct per transformed glyf / loca
+// pair, an hmtx unit of the group's one hmtx launch per transformed hmtx, a descriptor of the
+// assembly launch per table that a member lists, and a wave of the directory launch per member,
+// which writes its directory behind the TTC header and its own word of that header.
+// mib_debug_ttc_assemble runs the two assembly kernels alone over one collection.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -37,10 +44,10 @@ namespace woff2file {
 
 constexpr int kWave = 64;
 constexpr uint32_t kAsmSpread = 256;   // blocks per table at most (each walks its tiles)
-constexpr uint32_t kPeekBytes = 40;    // a font's row of the peek: 36 + 2, padded
+constexpr uint32_t kPeekBytes = 40;    // a row of the peek: 36 + 2, padded
 
-// One font of the peek: the transformed glyf table's first 36 bytes and hhea's bytes 34..35
-// (null: not wanted; the row's bytes are then zero).
+// One row of the peek: a transformed glyf table's first 36 bytes (a row per glyf / loca pair) or
+// an hhea's bytes 34..35 (a row per hmtx unit); null: not wanted, the row's bytes are then zero.
 struct PeekFont {
   const uint8_t *glyf, *hhea34;
 };
@@ -107,14 +114,29 @@ __global__ __launch_bounds__(kAsmThreads) void sfnt_assemble_kernel(const AsmDes
 // One wave per font (blockIdx.x).  The offset table and the records (their place, 12 + 16 r, is a
 // multiple of 4: four word stores each); every lane sums the words it writes and its records'
 // table sums, the wave's total is the file's sum, and head's checkSumAdjustment follows from it.
+// A member of a collection is a font here: its directory lies at dir_off in the TTC (a multiple
+// of 4, not of 16: word stores throughout), its records reach the sums of tables that other
+// members may list too, and it stores the shared head's checkSumAdjustment only where adjust_at
+// says so (one wave per head: the same bytes on every run).  Each member stores its own word of
+// the TTC header, member 0 the rest of it; the header takes part in no sum.
 __global__ __launch_bounds__(kWave) void sfnt_directory_kernel(const DirFont *fonts, const DirRec *all_recs,
                                                               const uint32_t *all_sums, uint8_t *all_out) {
   const DirFont f = fonts[blockIdx.x];
   const DirRec *recs = all_recs + f.first_rec;
   const uint32_t *sums = all_sums + f.first_sum;
-  uint8_t *out = all_out + f.out_base;
+  uint8_t *file = all_out + f.out_base, *out = file + f.dir_off;
   const int lane = threadIdx.x;
   uint32_t *o = reinterpret_cast<uint32_t *>(out);
+  if (f.ttc_index != kNoZero && lane == kWave - 1) {
+    uint32_t *h = reinterpret_cast<uint32_t *>(file);
+    h[3 + f.ttc_index] = be_word(f.dir_off);
+    if (f.ttc_index == 0) {
+      h[0] = be_word(kFlavorTtc);
+      h[1] = be_word(f.ttc_version);
+      h[2] = be_word(f.ttc_fonts);
+      if (f.ttc_version == kTtcVersion2) h[3 + f.ttc_fonts] = h[4 + f.ttc_fonts] = h[5 + f.ttc_fonts] = 0;
+    }
+  }
   uint32_t acc = 0;
   if (lane == 0) {
     const uint32_t w0 = f.flavor, w1 = (f.num << 16) | f.range, w2 = (f.selector << 16) | f.shift;
@@ -134,7 +156,7 @@ __global__ __launch_bounds__(kWave) void sfnt_directory_kernel(const DirFont *fo
     acc += rec.tag + cs + rec.dst_off + rec.len + cs;   // the record's words, and the table's own
   }
   acc = wave_sum(acc);
-  if (lane == 0 && f.adjust_at != kNoZero) *reinterpret_cast<uint32_t *>(out + f.adjust_at) = be_word(kHeadMagic - acc);
+  if (lane == 0 && f.adjust_at != kNoZero) *reinterpret_cast<uint32_t *>(file + f.adjust_at) = be_word(kHeadMagic - acc);
 }
 
 // A thread per font, in the shape of the decoder's peek_heads_kernel: what the host needs of every
@@ -176,15 +198,15 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 // table's bytes on the device.  The output buffer (l.out_bytes; font f at its out_base) is left
 // at *d_out_p (in m); nothing is synchronised, and the caller keeps `l` until the stream is.
 int assemble_device(hipStream_t st, Timer &tm, DevMem &m, const Launch &l, uint8_t **d_out_p) {
-  const size_t nt = l.descs.size(), nf = l.fonts.size();
+  const size_t nt = l.descs.size(), nr = l.recs.size(), nf = l.fonts.size();   // (nr != nt: a collection's shared tables)
   AsmDesc *d_descs = m.take<AsmDesc>(nt);
-  DirRec *d_recs = m.take<DirRec>(nt);
+  DirRec *d_recs = m.take<DirRec>(nr);
   DirFont *d_fonts = m.take<DirFont>(nf);
   uint32_t *d_sums = m.take<uint32_t>(nt);
   uint8_t *d_out = m.take<uint8_t>((size_t)l.out_bytes);
   if (!d_descs || !d_recs || !d_fonts || !d_sums || !d_out) return MIB_E_OUT_OF_MEMORY;
   if (hipMemcpyAsync(d_descs, l.descs.data(), sizeof(AsmDesc) * nt, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_recs, l.recs.data(), sizeof(DirRec) * nt, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(d_recs, l.recs.data(), sizeof(DirRec) * nr, hipMemcpyHostToDevice, st) != hipSuccess ||
       hipMemcpyAsync(d_fonts, l.fonts.data(), sizeof(DirFont) * nf, hipMemcpyHostToDevice, st) != hipSuccess ||
       hipMemsetAsync(d_sums, 0, sizeof(uint32_t) * nt, st) != hipSuccess)
     return MIB_E_NO_DEVICE;
@@ -203,8 +225,7 @@ int assemble_device(hipStream_t st, Timer &tm, DevMem &m, const Launch &l, uint8
 // The plan a file of these k tables, all with the null transform, would give, before layout().
 // src_off: the table's place in the font's source bytes (misalign: from a 16-byte boundary on);
 // stream_len: how many those are.
-bool plan_of_tables(uint32_t flavor, const uint32_t *tags, const mib_span *tables, const uint8_t *misalign, size_t k,
-                    Plan *pl) {
+bool plan_sources(uint32_t flavor, const uint32_t *tags, const mib_span *tables, const uint8_t *misalign, size_t k, Plan *pl) {
   if (k == 0 || k > 65535) return false;
   pl->flavor = flavor;
   pl->t.clear();
@@ -221,6 +242,39 @@ bool plan_of_tables(uint32_t flavor, const uint32_t *tags, const mib_span *table
     if (tags[i] == kHeadTag) pl->head = (uint32_t)i;
   }
   pl->stream_len = total;
+  return true;
+}
+
+// The same tables as a collection's directory (repeated tags allowed), listed by n_fonts members:
+// member f has counts[f] tables, its indices taken in order from `indices`.  Laid out.
+bool plan_of_collection(uint32_t version, const uint32_t *tags, const mib_span *tables, const uint8_t *misalign, size_t k,
+                        const uint32_t *flavors, const uint32_t *counts, const uint32_t *indices, size_t n_fonts, Plan *pl) {
+  if ((version != kTtcVersion1 && version != kTtcVersion2) || n_fonts == 0 || n_fonts > 65535) return false;
+  if (!plan_sources(kFlavorTtc, tags, tables, misalign, k, pl)) return false;
+  pl->head = kNoTable;
+  pl->ttc_version = version;
+  pl->fonts.clear();
+  uint64_t dirs = 0;
+  size_t first = 0;
+  for (size_t f = 0; f < n_fonts; f++) {
+    dirs += 12 + 16 * (uint64_t)counts[f];
+    if (counts[f] == 0 || dirs > kMaxDirectoryBytes) return false;
+    pl->fonts.push_back(Member{flavors[f], {}, kNoTable, false, 0});
+    for (uint32_t i = 0; i < counts[f]; i++) {
+      if (indices[first + i] >= k) return false;
+      pl->fonts.back().order.push_back(indices[first + i]);
+    }
+    first += counts[f];
+  }
+  pl->pairs.clear();
+  pl->hunits.clear();
+  pl->unit.assign(k, kNoTable);
+  return collection_members(pl) && layout_units(pl, nullptr, nullptr, nullptr);
+}
+
+bool plan_of_tables(uint32_t flavor, const uint32_t *tags, const mib_span *tables, const uint8_t *misalign, size_t k,
+                    Plan *pl) {
+  if (!plan_sources(flavor, tags, tables, misalign, k, pl)) return false;
   pl->order.resize(k);
   for (size_t i = 0; i < k; i++) pl->order[i] = (uint32_t)i;
   std::sort(pl->order.begin(), pl->order.end(), [&](uint32_t a, uint32_t b) { return pl->t[a].tag < pl->t[b].tag; });
@@ -229,15 +283,14 @@ bool plan_of_tables(uint32_t flavor, const uint32_t *tags, const mib_span *table
   return layout(pl, 0, 0, 0);
 }
 
-struct BatchFont {   // a file of the group whose stream decoded
+struct BatchFont {   // a file of the group whose stream decoded: a single font or a collection
   size_t slot;       // in the call's arrays
   Plan *pl;
   const uint8_t *d_stream;
-  const uint8_t *hdr;   // the transformed glyf table's first 36 bytes (host), where it has one
-  uint32_t nhm;
-  uint8_t *d_glyf, *d_loca, *d_hmtx;
-  size_t glyf_b, loca_b, hmtx_b;
-  long hm;             // its place in the hmtx launch, or -1
+  size_t row0;       // its rows of the peek: one per pair, then one per hmtx unit
+  std::vector<const uint8_t *> glyfs, locas, hmtxs;   // device: per pair, per pair, per hmtx unit
+  std::vector<uint64_t> glyf_b, loca_b, hmtx_b;
+  std::vector<long> hm;   // per hmtx unit: its place in the hmtx launch, or -1
   uint64_t out_base;
   bool alive;
 };
@@ -286,18 +339,35 @@ int decode_group(mib_ctx *c, hipStream_t st, const mib_span *files, std::vector<
       status[idx[i]] = s;
       if (s) continue;
       Plan *pl = &plans[idx[i]];
-      const bool short_glyf = glyf_transformed(*pl) && pl->t[pl->glyf].src_len < (uint32_t)mib::woff2inv::kHeaderBytes;
+      bool short_glyf = false;
+      for (const Pair &p : pl->pairs) short_glyf |= pl->t[p.glyf].src_len < (uint32_t)mib::woff2inv::kHeaderBytes;
       if (short_glyf) {
         status[idx[i]] = MIB_E_INVALID_ARG;
         continue;
       }
-      fonts.push_back(BatchFont{idx[i], pl, d_streams + pack.slot_off[i], nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0, -1, 0, true});
+      BatchFont f;
+      f.slot = idx[i];
+      f.pl = pl;
+      f.d_stream = d_streams + pack.slot_off[i];
+      f.row0 = 0;
+      f.glyfs.assign(pl->pairs.size(), nullptr);
+      f.locas.assign(pl->pairs.size(), nullptr);
+      f.hmtxs.assign(pl->hunits.size(), nullptr);
+      f.glyf_b.assign(pl->pairs.size(), 0);
+      f.loca_b.assign(pl->pairs.size(), 0);
+      f.hmtx_b.assign(pl->hunits.size(), 0);
+      f.hm.assign(pl->hunits.size(), -1);
+      f.out_base = 0;
+      f.alive = true;
+      fonts.push_back(std::move(f));
     }
-    // the headers the host sizes the reconstructed tables from: one launch, one read-back
-    for (const BatchFont &f : fonts)
-      if (glyf_transformed(*f.pl))
-        peek.push_back(PeekFont{f.d_stream + f.pl->t[f.pl->glyf].src_off,
-                                hmtx_transformed(*f.pl) ? f.d_stream + f.pl->t[f.pl->hhea].src_off + 34 : nullptr});
+    // the headers the host sizes the reconstructed tables from: one launch, one read-back; a row
+    // per transformed glyf pair (the table's header) and per hmtx unit (its hhea's numberOfHMetrics)
+    for (BatchFont &f : fonts) {
+      f.row0 = peek.size();
+      for (const Pair &p : f.pl->pairs) peek.push_back(PeekFont{f.d_stream + f.pl->t[p.glyf].src_off, nullptr});
+      for (const HmtxUnit &u : f.pl->hunits) peek.push_back(PeekFont{nullptr, f.d_stream + f.pl->t[u.hhea].src_off + 34});
+    }
     if (!peek.empty()) {
       PeekFont *d_peek = gm.take<PeekFont>(peek.size());
       uint8_t *d_rows = gm.take<uint8_t>(kPeekBytes * peek.size());
@@ -316,53 +386,60 @@ int decode_group(mib_ctx *c, hipStream_t st, const mib_span *files, std::vector<
         rc = MIB_E_NO_DEVICE;
         break;
       }
-      size_t q = 0;
-      for (BatchFont &f : fonts)
-        if (glyf_transformed(*f.pl)) {
-          f.hdr = rows.data() + kPeekBytes * q++;
-          f.nhm = ((uint32_t)f.hdr[36] << 8) | f.hdr[37];
-        }
     }
-    // glyf and loca, font after font: a font's temporaries go before the next one's come
+    // glyf and loca, pair after pair: a pair's temporaries go before the next one's come
     const auto loop0 = std::chrono::steady_clock::now();
     for (BatchFont &f : fonts) {
-      if (!glyf_transformed(*f.pl)) continue;
-      const Table &g = f.pl->t[f.pl->glyf];
-      DevMem tmp;
-      const int r = mib::woff2dev::reconstruct_glyf_device(st, tm, tmp, gm, f.hdr, f.d_stream + g.src_off, g.src_len,
-                                                           &f.d_glyf, &f.glyf_b, &f.d_loca, &f.loca_b);
-      hipStreamSynchronize(st);   // (its last kernels read the temporaries)
-      if (r == MIB_E_NO_DEVICE) {
-        rc = r;
-        break;
+      for (size_t p = 0; p < f.pl->pairs.size() && f.alive && !rc; p++) {
+        const Table &g = f.pl->t[f.pl->pairs[p].glyf];
+        DevMem tmp;
+        uint8_t *d_glyf = nullptr, *d_loca = nullptr;
+        size_t glyf_b = 0, loca_b = 0;
+        const int r = mib::woff2dev::reconstruct_glyf_device(st, tm, tmp, gm, rows.data() + kPeekBytes * (f.row0 + p),
+                                                             f.d_stream + g.src_off, g.src_len, &d_glyf, &glyf_b, &d_loca, &loca_b);
+        hipStreamSynchronize(st);   // (its last kernels read the temporaries)
+        f.glyfs[p] = d_glyf, f.locas[p] = d_loca, f.glyf_b[p] = glyf_b, f.loca_b[p] = loca_b;
+        if (r == MIB_E_NO_DEVICE) {
+          rc = r;
+        } else if (r) {
+          status[f.slot] = r;
+          f.alive = false;
+        }
       }
-      if (r) {
-        status[f.slot] = r;
-        f.alive = false;
-      }
+      if (rc) break;
     }
     g_batch_ms[0] += ms_since(loop0);
     if (rc) break;
-    // hmtx: every font that has a transformed one, in one launch
+    // hmtx: every unit of every file, in one launch
     size_t hm_bytes = 0;
     uint32_t most_ng = 0;
     std::vector<size_t> hm_at;
     for (BatchFont &f : fonts) {
-      if (!f.alive || !hmtx_transformed(*f.pl)) continue;
-      const Table &h = f.pl->t[f.pl->hmtx];
-      const uint32_t ng = ((uint32_t)f.hdr[4] << 8) | f.hdr[5];
-      uint32_t long_loca = 0;
-      if (!mib::woff2inv::hmtx_shape_ok(h.src_len, f.glyf_b, f.loca_b, ng, f.nhm, &long_loca)) {
-        status[f.slot] = MIB_E_INVALID_ARG;
-        f.alive = false;
-        continue;
+      const size_t np = f.pl->pairs.size(), first = hm.size(), bytes0 = hm_bytes;
+      for (size_t u = 0; u < f.pl->hunits.size() && f.alive; u++) {
+        const HmtxUnit &hu = f.pl->hunits[u];
+        const Table &h = f.pl->t[hu.hmtx];
+        const uint8_t *hdr = rows.data() + kPeekBytes * (f.row0 + hu.pair), *hh = rows.data() + kPeekBytes * (f.row0 + np + u);
+        const uint32_t ng = ((uint32_t)hdr[4] << 8) | hdr[5], nhm = ((uint32_t)hh[36] << 8) | hh[37];
+        uint32_t long_loca = 0;
+        if (!mib::woff2inv::hmtx_shape_ok(h.src_len, f.glyf_b[hu.pair], f.loca_b[hu.pair], ng, nhm, &long_loca)) {
+          status[f.slot] = MIB_E_INVALID_ARG;
+          f.alive = false;
+          break;
+        }
+        f.hm[u] = (long)hm.size();
+        f.hmtx_b[u] = 4 * (uint64_t)nhm + 2 * (uint64_t)(ng - nhm);
+        hm.push_back(HmtxFont{f.d_stream + h.src_off, h.src_len, f.glyfs[hu.pair], f.locas[hu.pair], nullptr,
+                              (uint32_t)f.glyf_b[hu.pair], long_loca, ng, nhm});
+        hm_at.push_back(hm_bytes);
+        hm_bytes = (hm_bytes + (size_t)f.hmtx_b[u] + 15) & ~(size_t)15;
+        most_ng = ng > most_ng ? ng : most_ng;
       }
-      f.hm = (long)hm.size();
-      f.hmtx_b = 4 * (size_t)f.nhm + 2 * (size_t)(ng - f.nhm);
-      hm.push_back(HmtxFont{f.d_stream + h.src_off, h.src_len, f.d_glyf, f.d_loca, nullptr, (uint32_t)f.glyf_b, long_loca, ng, f.nhm});
-      hm_at.push_back(hm_bytes);
-      hm_bytes = (hm_bytes + f.hmtx_b + 15) & ~(size_t)15;
-      most_ng = ng > most_ng ? ng : most_ng;
+      if (!f.alive) {   // a rejected file's units leave the launch (most_ng may stay above what is left)
+        hm.resize(first);
+        hm_at.resize(first);
+        hm_bytes = bytes0;
+      }
     }
     int *d_hm_bad = nullptr;
     if (!hm.empty()) {
@@ -375,16 +452,18 @@ int decode_group(mib_ctx *c, hipStream_t st, const mib_span *files, std::vector<
       }
       for (size_t q = 0; q < hm.size(); q++) hm[q].out = d_hm_out + hm_at[q];
       for (BatchFont &f : fonts)
-        if (f.alive && f.hm >= 0) f.d_hmtx = hm[(size_t)f.hm].out;
+        for (size_t u = 0; u < f.hm.size() && f.alive; u++) f.hmtxs[u] = hm[(size_t)f.hm[u]].out;
       hm_bad.assign(hm.size(), 0);
       hipMemsetAsync(d_hm_bad, 0, sizeof(int) * hm.size(), st);
       hipMemcpyAsync(d_hm, hm.data(), sizeof(HmtxFont) * hm.size(), hipMemcpyHostToDevice, st);
       mib::woff2dev::launch_hmtx(st, tm, d_hm, hm.size(), most_ng, d_hm_bad);
     }
-    // layout per font, then the two assembly kernels once over every font
+    // layout per file, then the two assembly kernels once over every font of every file
     for (BatchFont &f : fonts) {
       if (!f.alive) continue;
-      if (!layout(f.pl, f.glyf_b, f.loca_b, f.hmtx_b) || !add_font(&launch, *f.pl, FontSrc{f.d_stream, f.d_glyf, f.d_loca, f.d_hmtx})) {
+      const FontSrc src{f.d_stream, f.glyfs.empty() ? nullptr : f.glyfs[0], f.locas.empty() ? nullptr : f.locas[0],
+                        f.hmtxs.empty() ? nullptr : f.hmtxs[0], f.glyfs.data(), f.locas.data(), f.hmtxs.data()};
+      if (!layout_units(f.pl, f.glyf_b.data(), f.loca_b.data(), f.hmtx_b.data()) || !add_font(&launch, *f.pl, src)) {
         status[f.slot] = MIB_E_INVALID_ARG;
         f.alive = false;
         continue;
@@ -414,10 +493,12 @@ int decode_group(mib_ctx *c, hipStream_t st, const mib_span *files, std::vector<
     }
     // flags that do not fit the size; a loca entry that does not fit the glyf table
     for (BatchFont &f : fonts)
-      if (f.alive && f.hm >= 0 && hm_bad[(size_t)f.hm]) {
-        drop(&sfnt[f.slot]);
-        status[f.slot] = MIB_E_INVALID_ARG;
-      }
+      for (size_t u = 0; u < f.hm.size() && f.alive; u++)
+        if (hm_bad[(size_t)f.hm[u]]) {
+          drop(&sfnt[f.slot]);
+          status[f.slot] = MIB_E_INVALID_ARG;
+          f.alive = false;
+        }
     timed = true;
   } while (0);
   if (rc) hipStreamSynchronize(st);   // nothing of this group is in flight when its buffers go
@@ -525,6 +606,34 @@ extern "C" int mib_debug_sfnt_assemble_batch(const uint32_t *flavors, const uint
   if (hipStreamSynchronize(use.st) != hipSuccess && !use.rc) use.rc = MIB_E_NO_DEVICE;
   if (use.rc)
     for (size_t f = 0; f < k; f++) drop(&sfnt[f]);
+  use.timed = use.rc == 0;
+  return use.rc;
+}
+
+extern "C" int mib_debug_ttc_assemble(uint32_t version, const uint32_t *tags, const mib_span *tables,
+                                      const uint8_t *d_src_misalign, size_t k, const uint32_t *font_flavors,
+                                      const uint32_t *font_counts, const uint32_t *font_indices, size_t n_fonts, mib_buf *ttc) {
+  if (!ttc) return MIB_E_INVALID_ARG;
+  ttc->data = nullptr;
+  ttc->size = 0;
+  if (!tags || !tables || !font_flavors || !font_counts || !font_indices) return MIB_E_INVALID_ARG;
+  Plan pl;
+  if (!plan_of_collection(version, tags, tables, d_src_misalign, k, font_flavors, font_counts, font_indices, n_fonts, &pl))
+    return MIB_E_INVALID_ARG;
+  const size_t total = (size_t)pl.stream_len;
+  std::vector<uint8_t> stage(total);
+  for (size_t i = 0; i < k; i++)
+    if (tables[i].size) memcpy(stage.data() + pl.t[i].src_off, tables[i].data, tables[i].size);
+  Launch host;   // (declared before the scope: the launches read it until the stream is synchronised)
+  Call use(true);
+  if (!use.c) return MIB_E_NO_DEVICE;
+  uint8_t *d_src = use.m.take<uint8_t>(total), *d_out = nullptr;
+  if (!d_src) return use.rc = MIB_E_OUT_OF_MEMORY;
+  if (total && hipMemcpyAsync(d_src, stage.data(), total, hipMemcpyHostToDevice, use.st) != hipSuccess)
+    return use.rc = MIB_E_NO_DEVICE;
+  if (!add_font(&host, pl, FontSrc{d_src, nullptr, nullptr, nullptr})) return use.rc = MIB_E_INVALID_ARG;
+  if ((use.rc = assemble_device(use.st, use.tm, use.m, host, &d_out))) return use.rc;
+  use.rc = use.fetch(d_out + host.fonts[0].out_base, (size_t)pl.sfnt_len, ttc);
   use.timed = use.rc == 0;
   return use.rc;
 }

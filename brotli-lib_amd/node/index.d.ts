@@ -87,9 +87,9 @@ export declare function woff2TransformHmtx(ttf: Uint8Array): Uint8Array | null
 export declare function woff2ReconstructGlyf(data: Uint8Array): { glyf: Uint8Array, loca: Uint8Array }
 /** inverse of woff2TransformHmtx: the dropped side bearings are the glyphs' xMin in glyf / loca */
 export declare function woff2ReconstructHmtx(data: Uint8Array, glyf: Uint8Array, loca: Uint8Array, numGlyphs: number, numHMetrics: number): Uint8Array
-/** a .woff2 file (single font) -> the sfnt it stands for, decoded, reconstructed and assembled on the GPU (records sorted by tag, tables in the file's order, checksums computed); throws on a file that does not parse */
+/** a .woff2 file -> the sfnt it stands for, decoded, reconstructed and assembled on the GPU (records sorted by tag, tables in the file's order, checksums computed); a font collection (flavor ttcf) -> its TTC (the members' directories behind the TTC header, each shared table once); throws on a file that does not parse */
 export declare function woff2Decode(data: Uint8Array): Uint8Array
-/** woff2Decode of many files in shared GPU launches (one Brotli decode launch and one assembly launch per group of files): per slot the sfnt, or the Error woff2Decode(file) alone would have thrown */
+/** woff2Decode of many files, single fonts and collections in any slots, in shared GPU launches (one Brotli decode launch and one assembly launch per group of files): per slot the sfnt or TTC, or the Error woff2Decode(file) alone would have thrown */
 export declare function woff2DecodeBatch(files: Uint8Array[]): (Uint8Array | Error)[]
 export interface Woff2EncodeOptions {
   /** 0..11, default 11 */

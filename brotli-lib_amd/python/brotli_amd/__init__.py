@@ -211,6 +211,11 @@ def _L():
                                                           ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
             lib.mib_woff2_batch_last_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
             lib.mib_woff2_batch_last_ms.restype = None
+        if hasattr(lib, 'mib_debug_ttc_assemble'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_debug_ttc_assemble.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_Span),
+                                                   ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
+                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                                   ctypes.c_size_t, ctypes.POINTER(_Buf)]
         if hasattr(lib, 'mib_woff2_encode'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_woff2_encode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_Woff2EncOpts),
                                              ctypes.POINTER(_Buf)]
@@ -657,9 +662,12 @@ def woff2_reconstruct_hmtx(data, glyf, loca, num_glyphs, num_hmetrics):
 
 
 def woff2_decode(data):
-    """The sfnt a .woff2 file (W3C WOFF2, single font) stands for: the Brotli stream decoded, glyf,
-    loca and hmtx reconstructed and the font assembled on the GPU -- records sorted by tag, tables
-    in the file's order at 4-byte boundaries, checksums and head's checkSumAdjustment computed.
+    """The sfnt a .woff2 file (W3C WOFF2) stands for: the Brotli stream decoded, glyf, loca and
+    hmtx reconstructed and the font assembled on the GPU -- records sorted by tag, tables in the
+    file's order at 4-byte boundaries, checksums and head's checkSumAdjustment computed.  A font
+    collection (flavor ttcf) gives its TTC: the header, the members' directories back to back,
+    then every table that a member lists, once; a shared table has one checksum, and a shared
+    head carries the checkSumAdjustment of the last member that lists it.
     The file is untrusted: one that does not parse raises BrotliError (MIB_E_INVALID_ARG, or the
     decoder's code for a corrupt Brotli stream)."""
     data = _bytes(data)
@@ -696,7 +704,8 @@ def woff2_decode_batch(files):
     """woff2_decode of many files in shared launches (mib_woff2_decode_batch): the Brotli streams
     decode in one launch and the sfnts are assembled in one.  Returns a list with, per slot, the
     bytes woff2_decode(file) alone would have returned, or the BrotliError it would have raised
-    (not raised here: the other files go on).  The same file may stand in several slots."""
+    (not raised here: the other files go on).  The same file may stand in several slots, and a
+    collection in any slot beside single fonts."""
     keep = [_in(b) for b in files]
     k = len(keep)
     spans = (_Span * max(k, 1))(*[_Span(_addr(a) if n else None, n) for a, n, _ in keep])
@@ -803,6 +812,35 @@ def debug_sfnt_assemble_batch(fonts, misalign=None):
     if rc:
         raise _err(rc)
     return [_take(outs[i]) for i in range(k)]
+
+
+def debug_ttc_assemble(version, tables, fonts, misalign=None):
+    """Diagnostic (tests): woff2_decode's assembly kernels alone over a collection: tables =
+    [(tag, bytes)], its directory (tags may repeat); fonts = [(flavor, [index, ...])], each
+    member's tables by their indices; misalign as debug_sfnt_assemble takes it.  Returns the TTC."""
+    tables = [(bytes(tag), _bytes(data)) for tag, data in tables]
+    fonts = [(int(flavor) & 0xFFFFFFFF, [int(i) for i in idx]) for flavor, idx in fonts]
+    k, nf = len(tables), len(fonts)
+    flat = [i for _, idx in fonts for i in idx]
+    if any(len(tag) != 4 for tag, _ in tables) or (misalign is not None and len(misalign) != k) or \
+            any(i < 0 or i > 0xFFFFFFFF for i in flat):
+        raise _err(-101)   # MIB_E_INVALID_ARG
+    tags = (ctypes.c_uint32 * max(k, 1))(*[int.from_bytes(tag, 'big') for tag, _ in tables])
+    keep = [ctypes.create_string_buffer(data, len(data)) for _, data in tables]
+    spans = (_Span * max(k, 1))()
+    for i, b in enumerate(keep):
+        spans[i].data = ctypes.cast(b, ctypes.c_void_p).value
+        spans[i].size = len(tables[i][1])
+    mis = bytes(misalign) if misalign is not None else None
+    flavors = (ctypes.c_uint32 * max(nf, 1))(*[f for f, _ in fonts])
+    counts = (ctypes.c_uint32 * max(nf, 1))(*[len(idx) for _, idx in fonts])
+    indices = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
+    buf = _Buf()
+    rc = _L().mib_debug_ttc_assemble(int(version) & 0xFFFFFFFF, tags, spans, mis, k, flavors, counts, indices, nf,
+                                     ctypes.byref(buf))
+    if rc:
+        raise _err(rc)
+    return _take(buf)
 
 
 def part_stats(ctx=None):

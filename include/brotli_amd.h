@@ -302,17 +302,30 @@ int mib_woff2_reconstruct_glyf(const uint8_t *tglyf, size_t n, mib_buf *glyf, mi
 int mib_woff2_reconstruct_hmtx(const uint8_t *thmtx, size_t n, const uint8_t *glyf, size_t glyf_n,
                                const uint8_t *loca, size_t loca_n, uint32_t num_glyphs,
                                uint32_t num_hmetrics, mib_buf *out);
-/* A .woff2 file (W3C WOFF2, single font) -> the sfnt it stands for.  The Brotli stream is decoded
+/* A .woff2 file (W3C WOFF2) -> the sfnt it stands for; of a font collection (flavor ttcf), the
+ * OpenType collection (TTC; below).  The Brotli stream is decoded
  * and glyf, loca and hmtx are reconstructed (as the two functions above do) on the device, where
  * the sfnt is assembled as well: offset table, table records sorted by tag, then
  * the tables in the order of the file's directory, each at a 4-byte boundary and zero-padded;
  * table checksums computed, head's checkSumAdjustment set (the rest of head, flags bit 11
  * included, as in the file).  The file is untrusted: MIB_E_INVALID_ARG for a header or directory
- * that does not parse (a font collection, a repeated tag, an undefined transform version, a
- * malformed UIntBase128, lengths above 256 MiB ...), a stream that does not decode to exactly the
+ * that does not parse (a repeated tag in one font, an undefined transform version, a malformed
+ * UIntBase128, lengths above 256 MiB ...), a stream that does not decode to exactly the
  * directory's total, and whatever the reconstruct functions reject; the decoder's own negative
  * code for a corrupt Brotli stream.  Metadata and private blocks are ignored.  On any error
- * sfnt is {NULL, 0}. */
+ * sfnt is {NULL, 0}.
+ * A collection (DESIGN.md 4c "A font collection") gives a TTC: 'ttcf', the CollectionHeader's
+ * version, numFonts and the offsets of the fonts' offset tables (version 2.0: three zero words
+ * more, no DSIG); the fonts' directories back to back, each with its member's flavor and its
+ * records sorted by tag, offsets file-relative; then every directory entry that a font lists,
+ * once, in the directory's order.  A table shared by several fonts has one checksum; per font,
+ * its head's checkSumAdjustment is taken from that font's own directory and tables, and a head
+ * shared by several fonts carries the last font's.  Every transformed glyf / loca pair and hmtx
+ * is reconstructed.  MIB_E_INVALID_ARG also for a CollectionHeader that does not parse: a version
+ * other than 1.0 or 2.0, no fonts, a font without tables, an index past the directory, a tag
+ * twice in one font, a glyf entry without its loca right behind it (or a font that lists one of
+ * the two alone), a transformed hmtx whose fonts do not agree on its glyf and hhea, directories
+ * above 16 MiB together. */
 int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt);
 /* Diagnostic (tests): the assembly kernels alone.  k tables (tag, bytes) in host memory are laid
  * out as mib_woff2_decode lays a font out; d_src_misalign[i] in 0..15 is the misalignment table
@@ -320,10 +333,10 @@ int mib_woff2_decode(const uint8_t *woff2, size_t n, mib_buf *sfnt);
  * WOFF2 stream). */
 int mib_debug_sfnt_assemble(uint32_t flavor, const uint32_t *tags, const mib_span *tables,
                             const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt);
-/* k single-font .woff2 files -> their sfnts, in shared launches (DESIGN.md 4c "A batch of
- * files"): the Brotli streams of a group of files decode in one launch, the sfnts of a group are
- * assembled in one launch of each assembly kernel; glyf and loca are reconstructed font after
- * font.  sfnt[i] / status[i] are what mib_woff2_decode(files[i]) alone would have produced, byte
+/* k .woff2 files (single fonts and collections, in any slots) -> their sfnts or TTCs, in shared
+ * launches (DESIGN.md 4c "A batch of files"): the Brotli streams of a group of files decode in
+ * one launch, the sfnts and TTCs of a group are assembled in one launch of each assembly kernel;
+ * glyf and loca are reconstructed pair after pair.  sfnt[i] / status[i] are what mib_woff2_decode(files[i]) alone would have produced, byte
  * for byte and code for code: everything about one file (a container that does not parse, a
  * corrupt stream, a table the reconstruct functions reject) is that slot's status -- 0,
  * MIB_E_INVALID_ARG, the decoder's own negative code, or MIB_E_OUT_OF_MEMORY when the slot's host
@@ -342,6 +355,14 @@ void mib_force_woff2_group_bytes(uint64_t bytes);
  * tables, taken in order from tags / tables / d_src_misalign (as mib_debug_sfnt_assemble). */
 int mib_debug_sfnt_assemble_batch(const uint32_t *flavors, const uint32_t *counts, const uint32_t *tags,
                                   const mib_span *tables, const uint8_t *d_src_misalign, size_t k, mib_buf *sfnt);
+/* Diagnostic (tests): the assembly kernels alone over a collection.  The k tables are its
+ * directory (tags may repeat; taken as mib_debug_sfnt_assemble takes them); member f of n_fonts
+ * has font_counts[f] tables, their indices in order from font_indices.  MIB_E_INVALID_ARG for a
+ * version other than 1.0 or 2.0, no fonts or more than 65,535, a font without tables, an index at
+ * or past k, a tag twice in one font. */
+int mib_debug_ttc_assemble(uint32_t version, const uint32_t *tags, const mib_span *tables,
+                           const uint8_t *d_src_misalign, size_t k, const uint32_t *font_flavors,
+                           const uint32_t *font_counts, const uint32_t *font_indices, size_t n_fonts, mib_buf *ttc);
 
 /* An sfnt (TrueType or CFF flavoured, single font) -> a .woff2 file (W3C WOFF2), written on the
  * device (DESIGN.md 4c "Writing a file"): the font is uploaded once, glyf and hmtx are transformed
