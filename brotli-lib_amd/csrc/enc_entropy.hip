@@ -5,7 +5,9 @@
 // the only per-stream serial steps (carry, offsets, dist_ring) touch O(segments) values.
 #include <hipcub/hipcub.hpp>
 #include <cstdlib>
+#include <cstring>
 #include <algorithm>
+#include <vector>
 
 #include "enc_common.h"
 
@@ -2697,19 +2699,32 @@ void launch_cluster(hipStream_t st, const Job *jobs, Mb *mbs, int nmbs, uint32_t
   hipLaunchKernelGGL(cluster_kernel, dim3(nmbs * (sk.k[0] + 4)), dim3(kCluT), 0, st, jobs, mbs, nmbs, hl, hd, lit_tree_cap(),
                      sk.k[0], kd);
 }
-void launch_huffman(hipStream_t st, hipStream_t side, const Job *jobs, Mb *mbs, int nmbs, const uint32_t *hl,
-                    const uint32_t *hc, const uint32_t *hd, Codes *codes, uint8_t *trees, uint8_t *hdr) {
-  // one launch for every slot (two launches by alphabet size, the literal one with half the LDS,
-  // were measured: C4 6.0 -> 5.5 ms but C3 8.9 -> 10.2 -- the command / distance blocks, the
-  // longest, then ran as a tail of their own)
-  // blocks per metablock: the literal codes (at most the cap, or one per literal type), one per
-  // command type, the distance (type, cluster) slots
+// huffman_kernel's launch arithmetic, shared by the encoder (launch_huffman) and the diagnostic
+// entry mib_debug_prefix_codes (which sizes its fabricated metablocks by nl and kc).
+// blocks per metablock (nr): the literal codes (nl: at most the cap, or one per literal type),
+// four command and sixteen distance slots (types 0..3); the command types 4..kc-1 and the
+// distance types 4..7 are second items of the first blocks
+struct HuffGrid { int nl, kc, nr; };
+static HuffGrid huffman_grid() {
   const SplitK sk = split_k();
   // (command / distance: kMaxBT types, the widening pass may leave more than sk.k[1], sk.k[2])
   static const int kc = knob("MIB_TYPE_SIZING") ? sk.k[1] : kMaxBT, kdt = knob("MIB_TYPE_SIZING") ? sk.k[2] : kMaxBT;   // (experiments)
   (void)kdt;
-  const int nl = std::max(lit_tree_cap(), sk.k[0]), nr = nl + 4 + 4 * kDistCtx;   // (types 4..kc-1: second items)
-  hipLaunchKernelGGL(huffman_kernel<704>, dim3(nmbs * nr), dim3(64), 0, st, jobs, mbs, nmbs, hl, hc, hd, codes, trees, nl, kc, nr);
+  const int nl = std::max(lit_tree_cap(), sk.k[0]);
+  return HuffGrid{nl, kc, nl + 4 + 4 * kDistCtx};
+}
+static void launch_huffman_codes(hipStream_t st, const Job *jobs, Mb *mbs, int nmbs, const uint32_t *hl, const uint32_t *hc,
+                                 const uint32_t *hd, Codes *codes, uint8_t *trees) {
+  // one launch for every slot (two launches by alphabet size, the literal one with half the LDS,
+  // were measured: C4 6.0 -> 5.5 ms but C3 8.9 -> 10.2 -- the command / distance blocks, the
+  // longest, then ran as a tail of their own)
+  const HuffGrid g = huffman_grid();
+  hipLaunchKernelGGL(huffman_kernel<704>, dim3(nmbs * g.nr), dim3(64), 0, st, jobs, mbs, nmbs, hl, hc, hd, codes, trees, g.nl, g.kc,
+                     g.nr);
+}
+void launch_huffman(hipStream_t st, hipStream_t side, const Job *jobs, Mb *mbs, int nmbs, const uint32_t *hl,
+                    const uint32_t *hc, const uint32_t *hd, Codes *codes, uint8_t *trees, uint8_t *hdr) {
+  launch_huffman_codes(st, jobs, mbs, nmbs, hl, hc, hd, codes, trees);
   // the header reads the split's and the clustering's results, not the prefix codes (it writes
   // Mb.hdr_bits and the block-split codes, huffman_kernel Mb.tree_bits and the other codes)
   hipLaunchKernelGGL(mb_header_kernel, dim3(nmbs), dim3(64), 0, side, jobs, mbs, nmbs, hdr, codes);
@@ -2731,6 +2746,131 @@ void launch_offsets(hipStream_t st, Job *jobs, int njobs, Mb *mbs, Seg *segs, ui
 
 }  // namespace enc
 }  // namespace mib
+
+extern "C" mib_ctx *mib_default_ctx(void);
+extern "C" void mib_default_lock(int on);
+extern "C" void *mib_ctx_stream_of(mib_ctx *c);
+extern "C" int mib_ctx_device_of(mib_ctx *c);
+
+// Diagnostic (tests): huffman_kernel alone on chosen histograms.  They fill fabricated metablocks
+// of one job (NPOSTFIX 0, NDIRECT 0: 64 distance symbols): per metablock nl literal codes spread
+// over eight block types (code j of a metablock: type j % 8, cluster j / 8 -- so a block walks
+// the per-type counts to find its slot), kc command types, eight distance types of four codes;
+// command types 4.. and distance types 4..7 are the blocks' second items.  One launch, through
+// launch_huffman_codes; each histogram's tree_bits, depths, codes and serialised bytes come back.
+extern "C" int mib_debug_prefix_codes(const uint32_t *hist, const uint32_t *alphabet, size_t k, mib_buf *out) {
+  using namespace mib::enc;
+  if (!k || !hist || !alphabet || !out) return MIB_E_INVALID_ARG;
+  out->data = nullptr;
+  out->size = 0;
+  const HuffGrid g = huffman_grid();
+  const size_t per[3] = {(size_t)std::min(g.nl, kMaxBT * kLitCtx), (size_t)std::min(g.kc, kMaxBT), (size_t)kMaxBT * kDistCtx};
+  struct Place { uint32_t mb, slot, asize; size_t off; };   // histogram i: its metablock, code slot, counts at hist + off
+  std::vector<Place> place(k);
+  size_t cnt[3] = {0, 0, 0}, off = 0;
+  for (size_t i = 0; i < k; i++) {
+    const int cat = alphabet[i] == 256 ? 0 : alphabet[i] == 704 ? 1 : alphabet[i] == 64 ? 2 : -1;
+    if (cat < 0) return MIB_E_INVALID_ARG;
+    const size_t j = cnt[cat] % per[cat];
+    const uint32_t slot = cat == 0 ? (uint32_t)((j % kMaxBT) * kLitCtx + j / kMaxBT) : cat == 1 ? (uint32_t)(kCmdSlot + j) : (uint32_t)(kDistSlot + j);
+    place[i] = Place{(uint32_t)(cnt[cat] / per[cat]), slot, alphabet[i], off};
+    cnt[cat]++;
+    off += alphabet[i];
+  }
+  size_t nmbs = 1;
+  for (int c = 0; c < 3; c++) nmbs = std::max(nmbs, (cnt[c] + per[c] - 1) / per[c]);
+  if (nmbs > 256) return MIB_E_INVALID_ARG;   // (~1.5 MiB of histograms, codes and trees a metablock)
+  std::vector<Mb> mbs(nmbs);
+  memset(mbs.data(), 0, nmbs * sizeof(Mb));
+  for (size_t i = 0; i < k; i++) {
+    Mb &mb = mbs[place[i].mb];
+    const uint32_t s = place[i].slot;
+    if (s < (uint32_t)kCmdSlot) {
+      const uint32_t ty = s / kLitCtx;
+      mb.nbt[0] = std::max(mb.nbt[0], ty + 1);
+      mb.nlit_t[ty] = std::max(mb.nlit_t[ty], s % kLitCtx + 1);
+    } else if (s < (uint32_t)kDistSlot) {
+      mb.nbt[1] = std::max(mb.nbt[1], s - kCmdSlot + 1);
+    } else {
+      const uint32_t ty = (s - kDistSlot) / kDistCtx;
+      mb.nbt[2] = std::max(mb.nbt[2], ty + 1);
+      mb.ndist_t[ty] = std::max(mb.ndist_t[ty], (s - kDistSlot) % kDistCtx + 1);
+    }
+  }
+  for (Mb &mb : mbs)
+    for (int c = 0; c < 3; c++) mb.nbt[c] = std::max(mb.nbt[c], 1u);
+  struct Lock {
+    Lock() { mib_default_lock(1); }
+    ~Lock() { mib_default_lock(0); }
+  } use;
+  mib_ctx *c = mib_default_ctx();
+  if (!c) return MIB_E_NO_DEVICE;
+  if (hipSetDevice(mib_ctx_device_of(c)) != hipSuccess) return MIB_E_NO_DEVICE;
+  hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
+  const size_t hl_n = nmbs * kLitSlots * 256, hc_n = nmbs * kMaxBT * 704, hd_n = nmbs * kMaxBT * kDistCtx * 128;
+  const size_t trees_n = nmbs * (size_t)kTreeSlots * kTreeBytes;
+  const size_t need = 8 * 256 + sizeof(Job) + nmbs * sizeof(Mb) + (hl_n + hc_n + hd_n) * 4 + nmbs * sizeof(Codes) + trees_n;
+  uint8_t *buf = nullptr;
+  if (hipMalloc(&buf, need) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
+  struct FreeAtExit {
+    uint8_t *p;
+    ~FreeAtExit() { hipFree(p); }
+  } free_at_exit{buf};
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    at = (at + 255) & ~(size_t)255;
+    uint8_t *p = buf + at;
+    at += bytes;
+    return p;
+  };
+  Job *d_job = reinterpret_cast<Job *>(take(sizeof(Job)));
+  Mb *d_mbs = reinterpret_cast<Mb *>(take(nmbs * sizeof(Mb)));
+  uint32_t *hl = reinterpret_cast<uint32_t *>(take(hl_n * 4)), *hc = reinterpret_cast<uint32_t *>(take(hc_n * 4));
+  uint32_t *hd = reinterpret_cast<uint32_t *>(take(hd_n * 4));
+  Codes *d_codes = reinterpret_cast<Codes *>(take(nmbs * sizeof(Codes)));
+  uint8_t *d_trees = take(trees_n);
+  if (at > need) return MIB_E_OUT_OF_MEMORY;
+  Job job;
+  memset(&job, 0, sizeof(job));
+  bool ok = hipMemsetAsync(buf, 0, need, st) == hipSuccess;
+  ok = ok && hipMemcpyAsync(d_job, &job, sizeof(Job), hipMemcpyHostToDevice, st) == hipSuccess;
+  ok = ok && hipMemcpyAsync(d_mbs, mbs.data(), nmbs * sizeof(Mb), hipMemcpyHostToDevice, st) == hipSuccess;
+  for (size_t i = 0; i < k && ok; i++) {
+    const Place &p = place[i];
+    uint32_t *dst = p.slot < (uint32_t)kCmdSlot    ? hl + ((size_t)p.mb * kLitSlots + p.slot) * 256
+                    : p.slot < (uint32_t)kDistSlot ? hc + ((size_t)p.mb * kMaxBT + (p.slot - kCmdSlot)) * 704
+                                                   : hd + ((size_t)p.mb * kMaxBT * kDistCtx + (p.slot - kDistSlot)) * 128;
+    ok = hipMemcpyAsync(dst, hist + p.off, (size_t)p.asize * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+  }
+  if (!ok) return MIB_E_NO_DEVICE;
+  launch_huffman_codes(st, d_job, d_mbs, (int)nmbs, hl, hc, hd, d_codes, d_trees);
+  if (hipGetLastError() != hipSuccess) return MIB_E_NO_DEVICE;
+  std::vector<Codes> codes(nmbs);
+  std::vector<uint8_t> trees(trees_n);
+  ok = hipMemcpyAsync(mbs.data(), d_mbs, nmbs * sizeof(Mb), hipMemcpyDeviceToHost, st) == hipSuccess;
+  ok = ok && hipMemcpyAsync(codes.data(), d_codes, nmbs * sizeof(Codes), hipMemcpyDeviceToHost, st) == hipSuccess;
+  ok = ok && hipMemcpyAsync(trees.data(), d_trees, trees_n, hipMemcpyDeviceToHost, st) == hipSuccess;
+  ok = ok && hipStreamSynchronize(st) == hipSuccess;
+  if (!ok) return MIB_E_NO_DEVICE;
+  out->data = mib_buf_alloc(k * (size_t)MIB_PREFIX_CODE_RECORD);
+  if (!out->data) return MIB_E_OUT_OF_MEMORY;
+  out->size = k * (size_t)MIB_PREFIX_CODE_RECORD;
+  memset(out->data, 0, out->size);
+  for (size_t i = 0; i < k; i++) {
+    const Place &p = place[i];
+    const Codes &cd = codes[p.mb];
+    uint8_t *r = out->data + i * (size_t)MIB_PREFIX_CODE_RECORD;
+    const uint32_t bits = mbs[p.mb].tree_bits[p.slot];
+    memcpy(r, &bits, 4);
+    const uint8_t *dp = p.slot < (uint32_t)kCmdSlot ? cd.ld[p.slot] : p.slot < (uint32_t)kDistSlot ? cd.cd[p.slot - kCmdSlot] : cd.dd[p.slot - kDistSlot];
+    const uint16_t *cp = p.slot < (uint32_t)kCmdSlot ? cd.lc[p.slot] : p.slot < (uint32_t)kDistSlot ? cd.cc[p.slot - kCmdSlot] : cd.dcd[p.slot - kDistSlot];
+    memcpy(r + 4, dp, p.asize);
+    memcpy(r + 4 + 704, cp, (size_t)p.asize * 2);
+    memcpy(r + 4 + 704 + 2 * 704, trees.data() + ((size_t)p.mb * kTreeSlots + p.slot) * kTreeBytes, kTreeBytes);
+  }
+  return 0;
+}
+
 #ifdef MIB_PROF
 extern "C" int mib_debug_read_huff_prof(unsigned long long *out) {
   hipMemcpyFromSymbol(out, HIP_SYMBOL(mib::enc::g_huff_prof), sizeof(unsigned long long) * 12);

@@ -225,6 +225,8 @@ def _L():
         if hasattr(lib, 'mib_debug_match_records'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_debug_match_records.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
                                                     ctypes.POINTER(_Buf)]
+        if hasattr(lib, 'mib_debug_prefix_codes'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_debug_prefix_codes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
         lib.mib_default_ctx.restype = ctypes.c_void_p
         lib.mib_ctx_clear_times.argtypes = [ctypes.c_void_p]
         lib.mib_set_allocator.argtypes = [_ALLOC_FN, _FREE_FN, ctypes.c_void_p]
@@ -588,6 +590,31 @@ def debug_match_records(buffers, options=None):
         n = keep[i][1]
         a = np.frombuffer(_take(outs[i]), dtype='<u4')
         res.append(a.reshape(n, -1) if n else a.reshape(0, 4))
+    return res
+
+
+def debug_prefix_codes(histograms):
+    """Diagnostic (tests): the encoder's Huffman kernel alone on chosen histograms
+    (mib_debug_prefix_codes).  histograms: sequences of 256 (literal), 704 (command) or 64
+    (distance) counts.  Per histogram a dict: 'bits' (the serialised code's bit count), 'depths'
+    and 'codes' (lists over the alphabet) and 'bytes' (the 1024 bytes it was serialised into)."""
+    import numpy as np
+    k = len(histograms)
+    hs = [np.ascontiguousarray(np.asarray(h, dtype='<u4')) for h in histograms]
+    alpha = np.array([len(h) for h in hs], dtype='<u4')
+    flat = np.ascontiguousarray(np.concatenate(hs)) if k else np.zeros(0, '<u4')
+    out = _Buf()
+    rc = _L().mib_debug_prefix_codes(flat.ctypes.data, alpha.ctypes.data, k, ctypes.byref(out))
+    if rc:
+        raise _err(rc)
+    raw = _take(out)
+    rec = 4 + 704 + 2 * 704 + 1024   # MIB_PREFIX_CODE_RECORD
+    res = []
+    for i in range(k):
+        r, n = raw[i * rec:(i + 1) * rec], len(hs[i])
+        res.append({'bits': int.from_bytes(r[:4], 'little'), 'depths': list(r[4:4 + n]),
+                    'codes': np.frombuffer(r, dtype='<u2', count=n, offset=4 + 704).tolist(),
+                    'bytes': bytes(r[4 + 704 + 2 * 704:])})
     return res
 
 

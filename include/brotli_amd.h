@@ -240,6 +240,17 @@ void mib_debug_dp_launches(uint64_t out[4]);
  * the product build) little-endian u32, each length << 24 | distance with stream-relative
  * positions, valid entries first, longest last, zeros after. */
 int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out);
+/* Diagnostic (tests): the encoder's Huffman kernel alone on chosen histograms.  alphabet[i] is
+ * 256 (a literal code), 704 (a command code) or 64 (a distance code, NPOSTFIX 0 and NDIRECT 0);
+ * hist holds the k histograms back to back, histogram i as alphabet[i] u32 counts.  They are
+ * placed in fabricated metablocks -- per metablock as many literal codes as the encoder's launch
+ * has literal blocks, spread over eight block types, eight command types, eight distance types
+ * of four codes -- and the kernel runs once, with the encoder's own launch arithmetic.  *out
+ * receives k records of MIB_PREFIX_CODE_RECORD bytes, histogram i's at i * that: u32 bit count of
+ * the serialised code, u8 depth[704], u16 code[704] (both zero past the alphabet), then the
+ * 1024 bytes the kernel serialised the code into (LSB first, zero after the last bit). */
+#define MIB_PREFIX_CODE_RECORD (4 + 704 + 2 * 704 + 1024)
+int mib_debug_prefix_codes(const uint32_t *hist, const uint32_t *alphabet, size_t k, mib_buf *out);
 
 void mib_buf_free(mib_buf *b);
 /* The allocator behind every mib_buf the library returns (default malloc / free), in the

@@ -113,6 +113,103 @@ def probe(data, positions):
     return out
 
 
+class _TraceCode(ctypes.Structure):
+    _fields_ = [('kind', ctypes.c_int32), ('index', ctypes.c_int32), ('alphabet', ctypes.c_int32),
+                ('mb', ctypes.c_int32), ('begin', ctypes.c_int64), ('end', ctypes.c_int64),
+                ('hist', ctypes.POINTER(ctypes.c_uint32))]
+
+
+class _TraceMap(ctypes.Structure):
+    _fields_ = [('kind', ctypes.c_int32), ('mb', ctypes.c_int32), ('size', ctypes.c_int32),
+                ('ntrees', ctypes.c_int32), ('begin', ctypes.c_int64), ('end', ctypes.c_int64),
+                ('values', _P)]
+
+
+# OracleTraceCode.kind
+LITERAL, COMMAND, DISTANCE, BLOCK_TYPE, BLOCK_COUNT, CONTEXT_MAP = 0, 1, 2, 3, 6, 9
+KIND_NAMES = {0: 'literal', 1: 'command', 2: 'distance', 3: 'literal block type', 4: 'command block type',
+              5: 'distance block type', 6: 'literal block count', 7: 'command block count',
+              8: 'distance block count', 9: 'literal context map code', 10: 'distance context map code'}
+
+
+def trace(data, dictionary=None):
+    """decode `data` with the oracle's trace on.  Returns a dict: 'result' (the decoded bytes, or
+    the negative error code), 'codes' (every prefix code read: dicts of kind, index, alphabet, mb,
+    begin, end, hist -- a list of counts), 'maps' (both context maps of every compressed metablock:
+    kind, mb, size, ntrees, begin, end, values) and 'metablocks' (compressed, stored, metadata,
+    empty-last)."""
+    L = lib()
+    L.oracle_trace.argtypes = [ctypes.c_int]
+    L.oracle_trace.restype = None
+    L.oracle_trace_codes.argtypes = [ctypes.POINTER(ctypes.POINTER(_TraceCode))]
+    L.oracle_trace_codes.restype = ctypes.c_size_t
+    L.oracle_trace_maps.argtypes = [ctypes.POINTER(ctypes.POINTER(_TraceMap))]
+    L.oracle_trace_maps.restype = ctypes.c_size_t
+    L.oracle_trace(1)
+    try:
+        result = decode(data, out_size=-1, dictionary=dictionary)
+        pc, pm = ctypes.POINTER(_TraceCode)(), ctypes.POINTER(_TraceMap)()
+        codes = []
+        for i in range(L.oracle_trace_codes(ctypes.byref(pc))):
+            c = pc[i]
+            codes.append({'kind': c.kind, 'index': c.index, 'alphabet': c.alphabet, 'mb': c.mb, 'begin': c.begin,
+                          'end': c.end, 'hist': c.hist[:c.alphabet]})
+        maps = []
+        for i in range(L.oracle_trace_maps(ctypes.byref(pm))):
+            m = pm[i]
+            maps.append({'kind': m.kind, 'mb': m.mb, 'size': m.size, 'ntrees': m.ntrees, 'begin': m.begin,
+                         'end': m.end, 'values': list(m.values[:m.size])})
+        mbs = (ctypes.c_int32 * 4)()
+        L.oracle_trace_metablocks(mbs)
+    finally:
+        L.oracle_trace(0)
+    return {'result': result, 'codes': codes, 'maps': maps, 'metablocks': tuple(mbs)}
+
+
+def create_huffman_tree(hist, limit=15):
+    """the reference's createHuffmanTree: (depths, count limits tried)"""
+    n = len(hist)
+    h = (ctypes.c_uint32 * n)(*hist)
+    d = (ctypes.c_uint8 * n)()
+    f = lib().oracle_create_huffman_tree
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    attempts = f(h, n, limit, d)
+    return list(d), attempts
+
+
+def build_store_tree(hist):
+    """the reference's buildAndStoreHuffmanTree for one histogram over len(hist) symbols:
+    (bytes, bit count, depths, codes)"""
+    n = len(hist)
+    h = (ctypes.c_uint32 * n)(*hist)
+    d = (ctypes.c_uint8 * n)()
+    c = (ctypes.c_uint16 * n)()
+    cap = 2 * n + 64
+    out = (ctypes.c_uint8 * cap)()
+    f = lib().oracle_build_store_tree
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
+    f.restype = ctypes.c_int64
+    nbits = f(h, n, d, c, out, cap)
+    if nbits < 0:
+        raise RuntimeError('oracle_build_store_tree: output too small')
+    return bytes(out[:(nbits + 7) // 8]), nbits, list(d), list(c)
+
+
+def encode_context_map(values, ntrees):
+    """the reference's encodeContextMap of a decoded map over ntrees trees: (bytes, bit count)"""
+    n = len(values)
+    v = (ctypes.c_uint32 * n)(*values)
+    cap = 4 * n + 1024
+    out = (ctypes.c_uint8 * cap)()
+    f = lib().oracle_encode_context_map
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
+    f.restype = ctypes.c_int64
+    nbits = f(v, n, ntrees, out, cap)
+    if nbits < 0:
+        raise RuntimeError('oracle_encode_context_map: output too small')
+    return bytes(out[:(nbits + 7) // 8]), nbits
+
+
 def max_block_types():
     """the largest (literal, command, distance) block type counts of any metablock the oracle
     decoder has decoded on this thread since the last call"""

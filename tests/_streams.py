@@ -268,7 +268,7 @@ class Code:
 
 
 def make_code(used, alphabet, shape, rng, st):
-    """shape: {'depth': m or None, 'simple': bool, 'pad': n, 'select': 0/1, 'rle': bool}"""
+    """shape: {'depth': m or None, 'simple': bool, 'pad': n, 'select': 0/1, 'rle': bool, 'sorted': bool}"""
     depth = shape.get('depth')
     pad = shape.get('pad', 0)
     if (depth is None or depth <= 8) and len(used) <= 4 and max(len(used), pad, 1) <= 4 and shape.get('simple', True):
@@ -278,7 +278,7 @@ def make_code(used, alphabet, shape, rng, st):
             order.append(next(spare))
         n, select = len(order), shape.get('select', 0)
         ln = {1: [0], 2: [1, 1], 3: [1, 2, 2], 4: [1, 2, 3, 3] if select else [2, 2, 2, 2]}[n]
-        if rng is not None:
+        if rng is not None and not shape.get('sorted'):   # ('sorted': the symbols stay in ascending order)
             rng.shuffle(order)
         return Code(dict(zip(order, ln)), alphabet, simple=(order, select))
     return Code(lengths_for(used, alphabet, depth, rng, pad), alphabet, rle=shape.get('rle', True))

@@ -16,47 +16,13 @@ streams of the same data decoded on the GPU.
 """
 import functools
 
-import numpy as np
 import pytest
 
 import _oracle
 import brotli_amd
+from _split_inputs import lit_stress
 
 pytestmark = pytest.mark.gpu
-
-
-def lit_stress(n, seed):
-    rng = np.random.default_rng(seed)
-    # per class of the previous byte (p1 >> 6), a Zipf-like law over a permutation whose most
-    # likely values lie in the next class: the contexts predict very different bytes
-    draws = []   # per class: pre-drawn bytes of its law, taken in order
-    for k in range(4):
-        nxt = (k + 1) & 3
-        own = rng.permutation(np.arange(64 * nxt, 64 * nxt + 64))
-        rest = rng.permutation(np.setdiff1d(np.arange(256), own))
-        perm = np.concatenate([own, rest])
-        w = 1.0 / np.arange(1, 257) ** (0.8 + 0.15 * k)
-        cdf = np.cumsum(w / w.sum())
-        draws.append(perm[np.minimum(255, np.searchsorted(cdf, rng.random(n)))].tolist())
-    at = [0, 0, 0, 0]
-    out = bytearray()
-    prev = 0
-    while len(out) < n:
-        run = int(rng.integers(1, 200))
-        for _ in range(run):
-            k = prev >> 6
-            prev = draws[k][at[k]]
-            at[k] += 1
-            out.append(prev)
-        if len(out) > 64:
-            for _ in range(int(rng.integers(0, 5))):   # a run of copies
-                ln = int(rng.integers(4, 48))
-                d = int(rng.integers(1, 64)) if rng.random() < 0.3 else int(rng.integers(64, len(out)))
-                d = min(d, len(out))
-                for _ in range(ln):
-                    out.append(out[len(out) - d])
-                prev = out[-1]
-    return bytes(out[:n])
 
 
 @functools.lru_cache(maxsize=1)
