@@ -53,6 +53,7 @@ struct DecJob {
   uint64_t *prog;         // the stream's progress words (zeroed before the launch)
   int32_t pidx, nparts;
   int64_t total;          // the stream's decoded size (from the index)
+  int32_t in_place;       // out (whole-stream jobs): 1 decoded in the output slot, 2 began there and left
 };
 
 constexpr int kDecodeBlock = 64;                    // one wave per stream

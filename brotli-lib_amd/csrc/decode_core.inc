@@ -59,7 +59,8 @@ static __device__ const int8_t kBlockLenBits[26] = {2, 2, 2, 2, 3, 3, 3, 3, 4, 4
 enum : int {
   ST_INITED = 1, ST_BLOCK_START = 2, ST_COMPRESSED_BLOCK_START = 3, ST_MAIN_LOOP = 4, ST_READ_METADATA = 5,
   ST_COPY_UNCOMPRESSED = 6, ST_INSERT_LOOP = 7, ST_COPY_LOOP = 8, ST_USE_DICTIONARY = 9, ST_FINISHED = 10,
-  ST_INIT_WRITE = 12, ST_WRITE = 13, ST_COPY_FROM_COMPOUND = 14
+  ST_INIT_WRITE = 12, ST_WRITE = 13, ST_COPY_FROM_COMPOUND = 14,
+  ST_LEAVE_DIRECT = 15   // (not the reference's: in place, go back to the scratch ring, then next_running)
 };
 
 constexpr int kBlockTreesCap = 3091;   // engine.ts:163 Int32Array(3091)
@@ -119,7 +120,7 @@ struct Dec {
   int tab_cap;             // entries of the kernel's LDS table area
   int32_t *bt;             // block-type and block-count trees (HBM scratch, cold)
   uint8_t *ring_scratch;   // the block's HBM ring
-  int direct;              // ring == out: a single-metablock stream decodes in place
+  int direct;              // ring == out: the stream decodes in place (kDirect*, below)
   uint8_t *ctx_modes, *ctx_map, *dist_ctx_map;   // HBM scratch
   int trivial_lit_ctx, lit_tree_idx, cmd_tree_idx;
   int j, insert_len, copy_len, dist_code, distance;
@@ -156,6 +157,22 @@ struct Dec {
 // outstanding ring stores.
 typedef __attribute__((address_space(3))) Dec DecS;
 #define LANE ((int)threadIdx.x)
+// Dec::direct.  kDirectRing / kDirectSlot: the output slot is the ring (maybe_realloc_ring; a
+// part's output and a session's buffer are kDirectRing).  kDirectLeft: the stream began in place
+// and went back to the scratch ring part-way.
+constexpr int kDirectRing = 1, kDirectSlot = 2, kDirectMask = 3, kDirectLeft = 4;
+// kDirectSlot: the bytes a slot holds beyond the stream's announced total T.  The loops are
+// fenced at T there, and a store never starts at or beyond the fence:
+//  * the general loop cuts a literal run at `fence - pos`, and refuses (-9) a copy longer than
+//    the metablock's rest, which ends at T (pos + mbl == T at every command's copy);
+//  * the fast loop hands over every command with pos + insert_len + copy_len >= lim <= T;
+//  * a dictionary word starts below T (the metablock's rest is > 0 after the literals) and is at
+//    most 37 bytes with its transform (the reference's own ring slack): it ends below T + 37;
+//  * compound-dictionary streams are not decoded this way, stored metablocks are never final.
+// So 37 would do; the further 64 keep what the slot of the kDirectRing rule always had behind
+// the ring.  (MIB_IN_PLACE_SLACK, brotli_amd.h)
+constexpr int kDirectSlack = MIB_IN_PLACE_SLACK;
+static_assert(kDirectSlack >= 37, "a dictionary word may end 36 bytes past the fence");
 static_assert(sizeof(Lds) + sizeof(Dec) + 2 * kLdsTab <= 163840 / 4, "four streams per CU");
 static_assert(sizeof(Lds) + sizeof(Dec) + 2 * kLdsTabBig + 4 * (kBlockTreesCap + 1) <= 163840 - 1024, "one stream per CU");
 constexpr uint64_t kPartFailed = ~0ull;   // a part's progress word when it failed
@@ -341,8 +358,12 @@ __device__ __forceinline__ int64_t abs_bit(const DecS &s) { return (s.win_base +
 // The output byte at position p >= pos - 2 (a literal context byte).  A part never reads the
 // bytes before its start from the output: the previous part may still be writing them; they
 // come from its entry (0 before the stream start, as in the reference's zeroed ring).
+// In place (s.direct) nothing has wrapped, so a position below 0 is before the stream's start:
+// 0, which the reference reads at the end of its zeroed ring -- an index that in place was never
+// zeroed and may lie outside the slot.
 __device__ __forceinline__ int ctx_byte(const DecS &s, int p, int rmask) {
   if (s.part && p < s.part_start) return p < 0 ? 0 : (s.pctx >> (8 * (s.part_start - 1 - p))) & 0xFF;
+  if (p < 0 && (s.direct & kDirectMask)) return 0;
   return s.ring[p & rmask];
 }
 
@@ -835,13 +856,15 @@ __device__ __noinline__ void lit_block_switch(DecS &s) {
   s.clo2 = s.clo1 + 256;
 }
 
-// back to the block's own ring: its content so far is the output's first ring_size bytes
+// back to the block's own ring: its content so far is the output's first pos bytes, and zero
+// from there on (the in-place ring is never zero-filled; what the reference's fresh array holds
+// at and beyond pos is made here)
 __device__ void leave_direct(DecS &s) {
   const int n = s.ring_size + 37;
-  for (int k = LANE; k < n; k += 64) s.ring_scratch[k] = k < s.out_cap ? s.out[k] : 0;
+  for (int k = LANE; k < n; k += 64) s.ring_scratch[k] = k < s.pos && k < s.out_cap ? s.out[k] : 0;
   wave_sync();
   s.ring = s.ring_scratch;
-  s.direct = 0;
+  s.direct = kDirectLeft;
 }
 
 __device__ void maybe_realloc_ring(DecS &s) {   // :608-630 (the scratch slice is max-sized; copy semantics kept)
@@ -852,18 +875,36 @@ __device__ void maybe_realloc_ring(DecS &s) {   // :608-630 (the scratch slice i
     if (!s.input_end && new_size < 16384 && s.max_ring >= 16384) new_size = 16384;
   }
   if (new_size <= s.ring_size) return;
-  // A stream announced as one final metablock whose ring fits the output buffer decodes
-  // straight into the output: the ring's bytes [0, pos) are then exactly the output's,
-  // so every flush is an identity and the ring -> output copy disappears.
-  if (s.ring_size == 0 && s.input_end && s.out_flushed == 0 && (int64_t)new_size + 37 + 64 <= s.out_cap) {
+  // A stream announced as one final metablock decodes straight into the output: the ring's
+  // bytes [0, pos) are then exactly the output's, so every flush is an identity and the
+  // ring -> output copy disappears.  Two ways in:
+  //  * kDirectRing: the whole ring (+ its slack) fits the slot;
+  //  * kDirectSlot: what the stream announces (expected_total, its one MLEN) fits both the ring,
+  //    so that no wrap can be needed, and the slot less kDirectSlack.  The ring's sizes keep the
+  //    reference's values; decompress() fences the loops at expected_total instead of at them.
+  //    (Not with a compound dictionary: a copy from it that ends at the fence ends the call.)
+  // In place the ring is not zero-filled.  Every read of it is below pos, which is written:
+  // a copy's source starts at pos - distance with 0 < distance <= max_dist <= pos (hot_loop:
+  // `if (distance > max_dist)` leaves for the dictionary and distance 0, which reads at pos,
+  // leaves for the scratch ring; fast_loop: `distance <= 0 || distance > max_dist` hands
+  // over) and ends below pos or repeats what lies below it; the literal contexts at
+  // pos - 1, pos - 2 below 0 are ctx_byte's; the flush moves [0, pos); leave_direct makes
+  // the zeros at and beyond pos.
+  const bool first_final = s.ring_size == 0 && s.input_end && s.out_flushed == 0;
+  if (first_final && (int64_t)new_size + 37 + 64 <= s.out_cap) {
     s.ring = s.out;
-    s.direct = 1;
-  } else if (s.direct && (int64_t)new_size + 37 + 64 > s.out_cap) {
+    s.direct = kDirectRing;
+  } else if (first_final && s.cd_total == 0 && s.expected_total <= new_size &&
+             (int64_t)s.expected_total + kDirectSlack <= s.out_cap) {
+    s.ring = s.out;
+    s.direct = kDirectSlot;
+  } else if ((s.direct & kDirectMask) && (int64_t)new_size + 37 + 64 > s.out_cap) {
     leave_direct(s);
   }
-  // a fresh Uint8Array: bytes beyond the old size are zero
-  for (int k = s.ring_size + LANE; k < new_size + 37; k += 64) s.ring[k] = 0;
-  wave_sync();
+  if (!(s.direct & kDirectMask)) {   // a fresh Uint8Array: bytes beyond the old size are zero
+    for (int k = s.ring_size + LANE; k < new_size + 37; k += 64) s.ring[k] = 0;
+    wave_sync();
+  }
   s.ring_cap = new_size + 37;
   s.ring_size = new_size;
 }
@@ -1300,6 +1341,8 @@ __device__ __noinline__ int hot_loop(int fence_in, int rmask_in, int stop_at_bou
         LU8 *clut = (LU8 *)g_lds.ctx_lut;
         const int part = __builtin_amdgcn_readfirstlane(s.part), part_end = __builtin_amdgcn_readfirstlane(s.part_end);
         const int pstart = __builtin_amdgcn_readfirstlane(s.part_start), cover_lo = __builtin_amdgcn_readfirstlane(s.cover_lo);
+        // in place in a slot with a scratch ring to go back to (a part / a session has none)
+        const int in_place = part ? 0 : __builtin_amdgcn_readfirstlane(s.direct & kDirectMask);
         // The last two output bytes (the literal context) live in registers: reading them
         // back from the ring would wait for every outstanding ring store (vmcnt is in order).
         // (part mode: absolute positions -- before the stream start the context bytes are 0;
@@ -1690,6 +1733,15 @@ __device__ __noinline__ int hot_loop(int fence_in, int rmask_in, int stop_at_bou
             }
             j = 0;
             phase = ST_COPY_LOOP;
+            if (distance == 0 && in_place) {
+              // Only a damaged stream has distance 0 (a short code's ring entry minus its
+              // offset): the copy reads its own destination, at and beyond pos, where the
+              // reference's fresh ring holds zeros and the slot was never zeroed.  The copy is
+              // made in the scratch ring, whose bytes from pos on leave_direct zeroes.
+              s.next_running = ST_COPY_LOOP;
+              s.running = ST_LEAVE_DIRECT;
+              break;
+            }
             PMARK(2);
           }
           {   // copy (:1379-1433)
@@ -2298,8 +2350,9 @@ __device__ __noinline__ int fast_loop(int fence_in, int rmask_in) {
     if (max_dist != max_back && pos < max_back) max_dist = pos;
     else max_dist = max_back;
     const int src = (pos - distance) & rmask;
-    if (distance < 0 || distance > max_dist || copy_len > mbl - insert_len || src + copy_len >= rmask) {
-      // error, dictionary word or wrapping copy: redo the distance in the general loop
+    if (distance <= 0 || distance > max_dist || copy_len > mbl - insert_len || src + copy_len >= rmask) {
+      // error, distance 0 (a damaged stream's: the general loop knows where such a copy reads),
+      // dictionary word or wrapping copy: redo the distance in the general loop
       P = dP;
       F = dF;
       max_dist = dmax;
@@ -2539,6 +2592,9 @@ __device__ __forceinline__ int decompress(DecS &s, int8_t *dist_extra, int32_t *
   }
   int fence = s.ring_size;
   int rmask = s.ring_size - 1;
+  // kDirectSlot: the ring is larger than the slot, so the loops stop at the stream's announced
+  // total (kDirectSlack), not at the ring's fence
+  if (s.direct == kDirectSlot && s.expected_total < fence) fence = s.expected_total;
   while (s.running != ST_FINISHED) {
     if (++s.guard > s.guard_limit) return MIB_E_NO_PROGRESS;
     switch (s.running) {
@@ -2554,6 +2610,7 @@ __device__ __forceinline__ int decompress(DecS &s, int8_t *dist_extra, int32_t *
         if ((r = read_next_mb_header(s)) < 0) return r;
         fence = s.ring_size;
         if (s.pos + s.mbl <= s.ring_size) fence = 0x7FFFFFFF;
+        if (s.direct == kDirectSlot && s.expected_total < fence) fence = s.expected_total;
         rmask = s.ring_size - 1;
         continue;
       case ST_COMPRESSED_BLOCK_START:
@@ -2678,8 +2735,29 @@ __device__ __forceinline__ int decompress(DecS &s, int8_t *dist_extra, int32_t *
         s.running = ST_BLOCK_START;
         continue;
       }
+      case ST_LEAVE_DIRECT:   // (hot_loop: a copy that reads at and beyond pos)
+        if (s.direct == kDirectSlot) fence = 0x7FFFFFFF;   // the ring's own, as in ST_BLOCK_START
+        leave_direct(s);
+        s.running = s.next_running;
+        continue;
       case ST_INIT_WRITE:
         if (s.part) {   // part mode decodes into the output itself: nothing to flush
+          s.running = s.next_running;
+          continue;
+        }
+        if (s.direct == kDirectSlot && s.next_running != ST_FINISHED) {
+          // The announced total is reached, where the ring has no fence (its one metablock
+          // fits it: 0x7FFFFFFF above), so there is no flush here.  A stream that is done
+          // stores nothing more: its next step finds the literals complete (j == insert_len,
+          // the metablock's rest then 0) or, after a dictionary word, the rest <= 0, and goes
+          // to the next header.  Any other (a literal run beyond the total) goes on in the
+          // scratch ring, behind the ring's own fence, as if it had never been in place.
+          const bool done = (s.next_running == ST_INSERT_LOOP && s.j >= s.insert_len) ||
+                            (s.next_running == ST_MAIN_LOOP && s.mbl <= 0);
+          if (!done) {
+            leave_direct(s);
+            fence = 0x7FFFFFFF;
+          }
           s.running = s.next_running;
           continue;
         }
@@ -2690,7 +2768,7 @@ __device__ __forceinline__ int decompress(DecS &s, int8_t *dist_extra, int32_t *
         if ((r = write_ring(s)) != 0) return r;
         if (s.pos >= s.max_back) s.max_dist = s.max_back;
         if (s.pos >= s.ring_size) {
-          if (s.direct && (s.next_running != ST_FINISHED || s.pos > s.ring_size)) leave_direct(s);
+          if ((s.direct & kDirectMask) && (s.next_running != ST_FINISHED || s.pos > s.ring_size)) leave_direct(s);
           if (s.pos > s.ring_size) {
             int extra = s.pos - s.ring_size;
             uint8_t v = 0;
@@ -2858,6 +2936,7 @@ __global__ __launch_bounds__(64) void decode_streams_kernel(DecJob *jobs, int nj
     if (lane == 0) {
       jobs[jb].status = rc < 0 ? rc : 0;
       jobs[jb].result_len = s.known_size ? job.out_size : s.out_flushed;
+      jobs[jb].in_place = (s.direct & kDirectMask) ? 1 : s.direct == kDirectLeft ? 2 : 0;
     }
     __syncthreads();
   }
@@ -2934,7 +3013,7 @@ __device__ int part_run(DecS &s, const DecJob &job, int8_t *dist_extra, int32_t 
   s.max_ring = 1 << job.max_ring_log;
   s.max_back = s.max_ring - 16;
   s.ring = job.out;
-  s.direct = 1;
+  s.direct = kDirectRing;
   s.ring_size = rs;
   s.ring_cap = rs + 37;
   s.expected_total = (int)job.total;

@@ -41,7 +41,7 @@ __device__ int stream_run(DecS &s, const StreamJob &job, StreamCtl *c, int8_t *d
   s.max_ring = 1 << job.lgwin;
   s.max_back = s.max_ring - 16;
   s.ring = job.buf;
-  s.direct = 1;
+  s.direct = kDirectRing;
   s.ring_size = 1 << 30;
   s.ring_cap = (int)job.buf_cap;
   s.expected_total = 1 << 30;

@@ -359,6 +359,8 @@ struct mib_ctx {
   bool ring_failed = false;
   // part decoding counters (streams decoded part-parallel / sent back to the serial decoder)
   uint64_t parts_used = 0, parts_fallback = 0;
+  // the last serial decode launch: streams that finished in their output slots / left them part-way
+  uint64_t in_place_done = 0, in_place_left = 0;
   // profiling
   int profiling = 0;   // 0 off, 1 every kernel, 2 the decoder's only (mib_ctx_set_profiling)
   std::vector<mib_kernel_time> times;
@@ -825,6 +827,12 @@ void mib_part_stats(mib_ctx *c, uint64_t *parallel, uint64_t *fallback) {
   if (fallback) *fallback = c ? c->parts_fallback : 0;
 }
 
+void mib_debug_in_place(mib_ctx *c, uint64_t *finished, uint64_t *left) {
+  if (!c) c = default_ctx();
+  if (finished) *finished = c ? c->in_place_done : 0;
+  if (left) *left = c ? c->in_place_left : 0;
+}
+
 // internal (encode.hip)
 mib_ctx *mib_default_ctx(void) { return default_ctx(); }
 // The host-memory entry points (here, encode.hip, woff2.hip) hold the default context for one
@@ -907,6 +915,7 @@ int mib_ctx_kernel_times(mib_ctx *c, mib_kernel_time *out, int max) {
 // decode k streams whose bytes are on the device; jobs[] describes them (host copy)
 static int decode_jobs(mib_ctx *c, std::vector<mib::DecJob> &jobs, hipStream_t stream) {
   size_t k = jobs.size();
+  c->in_place_done = c->in_place_left = 0;
   if (k == 0) return 0;
   int max_log = 10;
   for (auto &j : jobs) max_log = std::max(max_log, j.max_ring_log);
@@ -945,6 +954,10 @@ static int decode_jobs(mib_ctx *c, std::vector<mib::DecJob> &jobs, hipStream_t s
     c->add_time("decode_streams_kernel", ms);
     hipEventDestroy(e0);
     hipEventDestroy(e1);
+  }
+  for (auto &j : jobs) {
+    c->in_place_done += j.in_place == 1 && j.status == 0;
+    c->in_place_left += j.in_place == 2;
   }
   return 0;
 }
@@ -1203,7 +1216,8 @@ int mib_decode(const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, 
   }
   for (;;) {
     // room for the ring of a one-metablock stream (a power of two >= its size, + slack), so
-    // the kernel can decode in place instead of through its scratch ring
+    // the kernel can decode in place instead of through its scratch ring (a stream with a
+    // custom dictionary does so only when the whole ring fits: maybe_realloc_ring)
     uint64_t alloc = 1;
     while (alloc < cap) alloc <<= 1;
     alloc += 4096;
@@ -1256,7 +1270,8 @@ int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status) {
     ioff[i + 1] = ioff[i] + ((in[i].size + 255) & ~(size_t)255);
     int64_t est = mib_decoded_size(in[i].data, in[i].size);
     uint64_t cap = est > 0 ? (uint64_t)est : std::max<uint64_t>(1 << 16, 8 * (uint64_t)in[i].size);
-    ooff[i + 1] = ooff[i] + ((cap + 64 + 255) & ~(uint64_t)255);
+    // (+ the slack that lets a one-metablock stream decode in its slot, + the 64 behind every slot)
+    ooff[i + 1] = ooff[i] + ((cap + MIB_IN_PLACE_SLACK + 64 + 255) & ~(uint64_t)255);
   }
   uint8_t *d_in = mib_ctx_stage(c, 0, ioff[k] + 16), *d_out = mib_ctx_stage(c, 1, ooff[k] + 64);
   if (!d_in || !d_out) return MIB_E_OUT_OF_MEMORY;

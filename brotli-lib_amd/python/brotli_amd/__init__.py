@@ -222,6 +222,9 @@ def _L():
             lib.mib_woff2_encode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Woff2EncOpts),
                                                    ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_part_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        if hasattr(lib, 'mib_debug_in_place'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_debug_in_place.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+            lib.mib_debug_in_place.restype = None
         if hasattr(lib, 'mib_debug_match_records'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_debug_match_records.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
                                                     ctypes.POINTER(_Buf)]
@@ -875,6 +878,18 @@ def part_stats(ctx=None):
     DeviceContext, or the host API's default context"""
     a, b = ctypes.c_uint64(), ctypes.c_uint64()
     _L().mib_part_stats(ctx._c if ctx is not None else None, ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
+IN_PLACE_SLACK = 101   # MIB_IN_PLACE_SLACK: a slot of size + this lets a one-metablock stream decode in place
+
+
+def in_place_stats(ctx=None):
+    """Diagnostic (tests): (streams that finished in their output slots, streams that began there
+    and went back to the scratch ring) in the last serial decode launch of a DeviceContext, or
+    of the host API's default context (mib_debug_in_place)"""
+    a, b = ctypes.c_uint64(), ctypes.c_uint64()
+    _L().mib_debug_in_place(ctx._c if ctx is not None else None, ctypes.byref(a), ctypes.byref(b))
     return a.value, b.value
 
 

@@ -420,6 +420,15 @@ int mib_woff2_encode_batch(const mib_span *sfnts, size_t k, const mib_woff2_enc_
  * those it sent back to the serial decoder because a part did not check out. Diagnostic. */
 void mib_part_stats(mib_ctx *c, uint64_t *parallel, uint64_t *fallback);
 
+/* A stream that is one final metablock decodes in its output slot, with no pass through the
+ * decoder's scratch ring, when the slot holds its decoded size and this many bytes more (no
+ * custom dictionary).  Smaller slots decode to the same bytes through the ring. */
+#define MIB_IN_PLACE_SLACK 101
+/* Diagnostic: of the streams of a context's (NULL: the default one's) last serial decode launch,
+ * how many finished in their slots (status 0) and how many began there and went back to the
+ * ring, whatever they ended in. */
+void mib_debug_in_place(mib_ctx *c, uint64_t *finished, uint64_t *left);
+
 #ifdef __cplusplus
 }
 #endif
