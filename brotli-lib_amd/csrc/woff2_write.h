@@ -36,6 +36,8 @@
 // maxp of 6, numGlyphs above 0, a loca of numGlyphs + 1 entries.  (A malformed glyph is found on
 // the device.)  Checksums, the searchRange fields, record order, table alignment and table
 // overlap are not checked: each table is read through its own record.
+// (parse() answers 2 for ttcf because a collection is not a single font: its plan is
+// woff2_write_ttc.h's, which continues this list, and encode_batch sends it there.)
 #ifndef MIB_WOFF2_WRITE_H_
 #define MIB_WOFF2_WRITE_H_
 #include <stddef.h>
@@ -170,6 +172,20 @@ inline void put_base128(std::vector<uint8_t> *o, uint32_t v) {   // minimal: no 
   for (int g = groups - 1; g >= 0; g--) o->push_back((uint8_t)(((v >> (7 * g)) & 0x7F) | (g ? 0x80 : 0)));
 }
 
+// One directory entry of a laid-out table (a collection's entries are written the same way)
+inline void put_entry(std::vector<uint8_t> *dir, const Table &t) {
+  uint32_t known = 63;
+  for (uint32_t q = 0; q < 63; q++)
+    if (woff2file::kKnownTags[q] == t.tag) known = q;
+  const bool gl = t.tag == kGlyfTag || t.tag == kLocaTag;
+  const uint32_t ver = gl ? (t.state == kPlain ? 3 : 0) : t.state == kTrHmtx ? 1 : 0;
+  dir->push_back((uint8_t)(known | (ver << 6)));
+  if (known == 63)
+    for (int s = 24; s >= 0; s -= 8) dir->push_back((uint8_t)(t.tag >> s));
+  put_base128(dir, t.src_len);
+  if (t.state != kPlain) put_base128(dir, t.len);
+}
+
 // The places in the stream and the directory, once the transformed sizes are known.  tglyf_len:
 // the transformed glyf table's (ignored unless tr_glyf); thmtx_len: the transformed hmtx table's,
 // 0 where hmtx stays as it is (both side-bearing arrays differ, or it was never wanted).  False
@@ -186,16 +202,7 @@ inline bool layout(Plan *pl, uint64_t tglyf_len, uint64_t thmtx_len) {
     t.len = (uint32_t)len;
     at += len;
     if (at > woff2inv::kMaxInput) return false;
-    uint32_t known = 63;
-    for (uint32_t q = 0; q < 63; q++)
-      if (woff2file::kKnownTags[q] == t.tag) known = q;
-    const bool gl = t.tag == kGlyfTag || t.tag == kLocaTag;
-    const uint32_t ver = gl ? (t.state == kPlain ? 3 : 0) : t.state == kTrHmtx ? 1 : 0;
-    pl->dir.push_back((uint8_t)(known | (ver << 6)));
-    if (known == 63)
-      for (int s = 24; s >= 0; s -= 8) pl->dir.push_back((uint8_t)(t.tag >> s));
-    put_base128(&pl->dir, t.src_len);
-    if (t.state != kPlain) put_base128(&pl->dir, t.len);
+    put_entry(&pl->dir, t);
   }
   pl->stream_len = at;
   return true;

@@ -101,7 +101,7 @@ export interface Woff2EncodeOptions {
   /** transform hmtx where glyf is transformed and a side-bearing array equals the glyphs' xMin (default true) */
   transformHmtx?: boolean
 }
-/** a single-font sfnt -> its .woff2 file, written on the GPU (FONT-mode Brotli; tables in tag order, DSIG dropped; every byte but the Brotli stream is fixed); woff2Decode reads every file written; throws on a font that does not parse */
+/** an sfnt -> its .woff2 file, written on the GPU (FONT-mode Brotli; tables in tag order, DSIG dropped; every byte but the Brotli stream is fixed); an OpenType collection (TTC) -> the .woff2 file of flavor ttcf (every table once in one directory: tables of one tag, offset and length, or of one tag and length and equal bytes, are one entry; glyf and loca are shared as a pair; each member lists its entries in the CollectionHeader); woff2Decode reads every file written; throws on a font or collection that does not parse */
 export declare function woff2Encode(sfnt: Uint8Array, options?: Woff2EncodeOptions): Uint8Array
-/** woff2Encode of many fonts in shared GPU launches (one upload, one copy launch and one encode call per group of fonts): per slot the file, or the Error woff2Encode(font) alone would have thrown */
+/** woff2Encode of many fonts, single fonts and collections in any slots, in shared GPU launches (one upload, one compare launch where collections have tables to compare, one copy launch and one encode call per group of fonts): per slot the file, or the Error woff2Encode(font) alone would have thrown */
 export declare function woff2EncodeBatch(sfnts: Uint8Array[], options?: Woff2EncodeOptions): (Uint8Array | Error)[]

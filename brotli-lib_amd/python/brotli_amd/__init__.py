@@ -221,6 +221,9 @@ def _L():
                                              ctypes.POINTER(_Buf)]
             lib.mib_woff2_encode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Woff2EncOpts),
                                                    ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
+        if hasattr(lib, 'mib_debug_tables_equal'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_debug_tables_equal.argtypes = [ctypes.POINTER(_Span), ctypes.POINTER(_Span), ctypes.c_char_p,
+                                                   ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint8)]
         lib.mib_part_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         if hasattr(lib, 'mib_debug_in_place'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_debug_in_place.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
@@ -769,7 +772,11 @@ def woff2_encode(sfnt, options=None):
     (mib_woff2_encode).  options: quality, lgwin, transformGlyf, transformHmtx.  Every byte but the
     Brotli stream is fixed (tables in tag order, DSIG dropped); woff2_decode reads every file
     written.  A font that does not parse, or that the glyf transform rejects, raises BrotliError
-    (MIB_E_INVALID_ARG)."""
+    (MIB_E_INVALID_ARG).
+    An OpenType collection (TTC) becomes the .woff2 file of flavor ttcf: every table once in one
+    directory -- tables of one tag, offset and length, and tables of one tag and length whose bytes
+    the device finds equal, are one entry; glyf and loca are shared as a pair -- and each member's
+    index list in the CollectionHeader."""
     data = _bytes(sfnt)
     buf = _Buf()
     rc = _L().mib_woff2_encode(data, len(data), ctypes.byref(_woff2_enc_opts(options)), ctypes.byref(buf))
@@ -782,7 +789,8 @@ def woff2_encode_batch(sfnts, options=None):
     """woff2_encode of many fonts in shared launches (mib_woff2_encode_batch): one upload, one copy
     launch and one encode call per group of fonts.  Returns a list with, per slot, the file or the
     BrotliError woff2_encode(font) alone would have raised (not raised here: the other fonts go
-    on).  The same font may stand in several slots."""
+    on).  The same font may stand in several slots, and a collection in any slot beside single
+    fonts (it is one file and one stream of its group)."""
     keep = [_in(b) for b in sfnts]
     k = len(keep)
     spans = (_Span * max(k, 1))(*[_Span(_addr(a) if n else None, n) for a, n, _ in keep])
@@ -792,6 +800,27 @@ def woff2_encode_batch(sfnts, options=None):
     if rc:
         raise _err(rc)
     return [_err(st[i]) if st[i] else _take(outs[i]) for i in range(k)]
+
+
+def debug_tables_equal(pairs, misalign_a=None, misalign_b=None):
+    """Diagnostic (tests): the collection writer's compare kernel alone over pairs = [(a, b)], byte
+    strings of one length each; misalign_a[i] / misalign_b[i] in 0..15 are the misalignments the
+    two sides get in device memory (None: 0).  Returns [bool]: True where a and b are equal."""
+    pairs = [(_bytes(a), _bytes(b)) for a, b in pairs]
+    k = len(pairs)
+    if any(m is not None and len(m) != k for m in (misalign_a, misalign_b)):
+        raise _err(-101)   # MIB_E_INVALID_ARG
+    keep = [(ctypes.create_string_buffer(a, len(a)), ctypes.create_string_buffer(b, len(b))) for a, b in pairs]
+    sa, sb = (_Span * max(k, 1))(), (_Span * max(k, 1))()
+    for i, (a, b) in enumerate(keep):
+        sa[i].data, sa[i].size = ctypes.cast(a, ctypes.c_void_p).value, len(pairs[i][0])
+        sb[i].data, sb[i].size = ctypes.cast(b, ctypes.c_void_p).value, len(pairs[i][1])
+    differ = (ctypes.c_uint8 * max(k, 1))(*([2] * max(k, 1)))
+    rc = _L().mib_debug_tables_equal(sa, sb, bytes(misalign_a) if misalign_a is not None else None,
+                                     bytes(misalign_b) if misalign_b is not None else None, k, differ)
+    if rc:
+        raise _err(rc)
+    return [differ[i] == 0 for i in range(k)]
 
 
 def force_woff2_group_bytes(n):

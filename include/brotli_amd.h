@@ -394,19 +394,42 @@ int mib_debug_ttc_assemble(uint32_t version, const uint32_t *tags, const mib_spa
  *               a side-bearing array equals the glyphs' xMin; otherwise it is stored as it is.
  *               Unknown bits: MIB_E_INVALID_ARG.
  *   quality, lgwin  clamped as mib_enc_opts'.  o NULL: quality 11, lgwin 22, both transforms.
- * MIB_E_INVALID_ARG, before any device work, for: fewer than 12 bytes; a first tag of ttcf, wOF2 or
+ * MIB_E_INVALID_ARG, before any device work, for: fewer than 12 bytes; a first tag of wOF2 or
  * wOFF; numTables 0 or a directory past the input; a record whose offset + length runs past the
  * input; a tag twice; table lengths above 256 MiB in sum; exactly one of glyf and loca; nothing
  * left after dropping DSIG.  Checksums, searchRange fields, record order, alignment and overlap
  * of the input's tables are not checked.  mib_woff2_decode accepts every file written.  On any
- * error woff2 is {NULL, 0}.  mib_woff2_encode is the batch with k = 1. */
+ * error woff2 is {NULL, 0}.  mib_woff2_encode is the batch with k = 1.
+ * An OpenType collection (first tag ttcf, version 1.0 or 2.0) becomes the .woff2 file of flavor
+ * ttcf (DESIGN.md 4c "Writing a collection"): one directory over all members, each table in it
+ * once, and the CollectionHeader with each member's flavor and indices.  Two records are one
+ * table when they have the same tag, offset and length, or the same tag and length and equal
+ * bytes (compared on the device; the records' checkSum fields only choose what is compared).
+ * glyf and loca are shared as a pair (the same glyf with another loca, numGlyphs or
+ * indexToLocFormat is written twice).  Members in the collection's order, each one's tables in
+ * ascending tag order with loca directly behind glyf; an entry is appended the first time a
+ * member lists it.  DSIG is dropped from every member.  The transforms apply to every pair; to
+ * an hmtx entry where every member that lists it lists the same pair and the same hhea and the
+ * single-font conditions hold.  Every head of at least 18 bytes is stored with bytes 8..11 zero,
+ * and with flags bit 11 set when a member that lists it has a transformed pair.  The header's
+ * version is the first member's head's that has one; totalSfntSize counts the TTC header, the
+ * members' directories and each entry's origLength padded to 4.
+ * MIB_E_INVALID_ARG for a collection, before any device work: the header, an offset table or a
+ * directory past the input; a version other than 1.0 or 2.0; numFonts 0 or above 65,535, or a
+ * member's numTables 0; a record whose offset + length runs past the input; a tag twice in one
+ * member; directories (12 + 16 numTables per member) above 16 MiB in sum; lengths, summed once
+ * per distinct (offset, length), above 256 MiB; a member with exactly one of glyf and loca; a
+ * member with nothing left after dropping DSIG; more than 65,535 directory entries; with
+ * MIB_WOFF2_GLYF, a member with glyf that the transform rejects. */
 typedef struct { int quality; int lgwin; uint32_t transforms; } mib_woff2_enc_opts;
 #define MIB_WOFF2_GLYF 1u   /* glyf + loca */
 #define MIB_WOFF2_HMTX 2u
 int mib_woff2_encode(const uint8_t *sfnt, size_t n, const mib_woff2_enc_opts *o, mib_buf *woff2);
-/* k fonts in shared launches: per group of fonts (mib_force_woff2_group_bytes, counting sfnt
- * bytes) one upload, one copy launch over every untransformed table, one encode call over every
- * stream, one synchronisation for the downloads; the transforms run font after font.  woff2[i] /
+/* k fonts (single fonts and collections, in any slots) in shared launches: per group of fonts
+ * (mib_force_woff2_group_bytes, counting input bytes) one upload, one compare launch over every
+ * candidate of every collection (none where there is no candidate), one copy launch over every
+ * untransformed table, one encode call over every stream (a collection is one stream), one
+ * synchronisation for the downloads; the transforms run font after font.  woff2[i] /
  * status[i] as mib_woff2_decode_batch's: everything about one font is that slot's status (0,
  * MIB_E_INVALID_ARG, MIB_E_OUT_OF_MEMORY for the slot's host buffer) and leaves the others
  * running; the same font may stand in several slots.  Returns 0, or MIB_E_INVALID_ARG (a NULL
@@ -414,6 +437,12 @@ int mib_woff2_encode(const uint8_t *sfnt, size_t n, const mib_woff2_enc_opts *o,
  * MIB_E_OUT_OF_MEMORY (a group's device buffers); then every woff2[i] is {NULL, 0}.  k == 0, and a
  * call in which no font parses, need no device.  Holds the default context's lock. */
 int mib_woff2_encode_batch(const mib_span *sfnts, size_t k, const mib_woff2_enc_opts *o, mib_buf *woff2, int *status);
+/* Diagnostic (tests): the collection writer's compare kernel alone over k pairs of byte ranges,
+ * a[i] and b[i] of one size; misalign_a[i] / misalign_b[i] in 0..15 are the misalignments the
+ * ranges get in the device buffer (NULL: 0).  differ[i] becomes 1 where the ranges differ, else 0.
+ * MIB_E_INVALID_ARG for sizes that are not equal. */
+int mib_debug_tables_equal(const mib_span *a, const mib_span *b, const uint8_t *misalign_a, const uint8_t *misalign_b,
+                           size_t k, uint8_t *differ);
 
 /* Part-parallel decoding (streams this encoder marked with a part index):
  * how many streams a context (NULL: the default one) decoded part-parallel, and how many of

@@ -5,8 +5,14 @@ woff2_transform_glyf, woff2_transform_hmtx and brotliEncode (FONT mode, quality 
 container written in Python (tests/_woff2_file.write).  For k = 64 the device time of the batch's
 kernels (HIP events, default_profiling).  `--loop-only` uses only the entry points that existed
 before woff2_encode, so that the baseline can be taken on an older library (BROTLI_AMD_LIB).
+`--batch-only` times woff2_encode_batch alone (the rows that are re-measured against a parent
+library).  `--collection` adds the row of DESIGN.md 4c "Writing a collection": the two-member
+collection over enc-ttf (the source font of enc-ttf-hmtx; the members share every table but name)
+as one woff2_encode call, against woff2_encode_batch over its two members as single fonts -- what
+a caller could do before --, time and bytes; and the same collection with every table written
+twice (nothing shared by offset), whose call holds the compare launch (`w2enc_same`).
 One JSON line.
-    python3 scripts/woff2_encode_timing.py [--loop-only] [--ks 1,8,64] [--calls 5]"""
+    python3 scripts/woff2_encode_timing.py [--loop-only] [--batch-only] [--collection] [--ks 1,8,64] [--calls 5]"""
 import argparse
 import json
 import os
@@ -60,9 +66,38 @@ def by_hand(font):
     return wf.write(int.from_bytes(font[:4], 'big'), entries, comp)
 
 
+def collection_row(calls):
+    import _woff2_collection as wc
+    import _woff2_collection_write as cw
+    t = wf.sfnt_tables(ww._source('enc-ttf'))
+    name2 = bytes([t[b'name'][0]]) + t[b'name'][1:-1] + bytes([t[b'name'][-1] ^ 1])
+    a = sorted(t.items())
+    b = [(tag, name2 if tag == b'name' else data) for tag, data in a]
+    row = {}
+    for key, share in (('shared', True), ('unshared', False)):
+        ttc = cw.build_ttc(wc.V1, [(wc.V1, a), (wc.V1, b)], share=share)
+        members = [cw.member_sfnt(ttc, 0), cw.member_sfnt(ttc, 1)]
+        r = {'ttc_bytes': len(ttc), 'member_bytes': sum(len(m) for m in members), 'candidates': len(cw.candidates(ttc))}
+        r['collection_ms_min_max'] = timed(lambda: brotli_amd.woff2_encode(ttc), calls)
+        r['members_batch_ms_min_max'] = timed(lambda: brotli_amd.woff2_encode_batch(members), calls)
+        file = brotli_amd.woff2_encode(ttc)
+        r['collection_woff2_bytes'] = len(file)
+        r['directory_entries'] = int.from_bytes(file[12:14], 'big')
+        r['members_woff2_bytes'] = sum(len(f) for f in brotli_amd.woff2_encode_batch(members))
+        brotli_amd.default_profiling(True)
+        brotli_amd.woff2_encode(ttc)
+        r['kernel_us_launches'] = {n: [round(v[0] * 1e3, 1), v[1]] for n, v in sorted(brotli_amd.default_kernel_times().items())
+                                   if n.startswith('w2enc')}
+        brotli_amd.default_profiling(False)
+        row[key] = r
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--loop-only', action='store_true')
+    ap.add_argument('--batch-only', action='store_true')
+    ap.add_argument('--collection', action='store_true')
     ap.add_argument('--ks', default='1,8,64')
     ap.add_argument('--calls', type=int, default=5)
     a = ap.parse_args()
@@ -71,6 +106,11 @@ def main():
     for k in [int(v) for v in a.ks.split(',')]:
         fonts = [bench[i % len(bench)] for i in range(k)]
         row = {'sfnt_bytes': sum(len(f) for f in fonts)}
+        if a.batch_only:
+            row['batch_ms_min_max'] = timed(lambda: brotli_amd.woff2_encode_batch(fonts), a.calls)
+            row['batch_woff2_bytes'] = sum(len(f) for f in brotli_amd.woff2_encode_batch(fonts))
+            out['k'][str(k)] = row
+            continue
         row['loop_ms_min_max'] = timed(lambda: [by_hand(f) for f in fonts], a.calls)
         row['loop_woff2_bytes'] = sum(len(by_hand(f)) for f in fonts)
         if not a.loop_only:
@@ -84,6 +124,8 @@ def main():
                 row['kernel_us_launches'] = {n: [round(v[0] * 1e3, 1), v[1]] for n, v in sorted(brotli_amd.default_kernel_times().items())}
                 brotli_amd.default_profiling(False)
         out['k'][str(k)] = row
+    if a.collection:
+        out['collection'] = collection_row(a.calls)
     print(json.dumps(out))
 
 
