@@ -54,6 +54,8 @@ struct DecJob {
   int32_t pidx, nparts;
   int64_t total;          // the stream's decoded size (from the index)
   int32_t in_place;       // out (whole-stream jobs): 1 decoded in the output slot, 2 began there and left
+  int32_t dict_std;       // 1: a copy from `dict` may lie anywhere inside it (a prepared dictionary, shared_dict.h);
+                          // 0: the reference's rule, it ends at the dictionary's last byte
 };
 
 constexpr int kDecodeBlock = 64;                    // one wave per stream

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "parts.h"
+#include "shared_dict.h"
 #include "stream_session.h"
 #define RFC_CONST static __device__ const
 #include "rfc_tables.h"
@@ -134,6 +135,7 @@ struct Dec {
   // compound dictionary
   const uint8_t *cd;
   int cd_total, cd_br_offset, cd_br_length, cd_br_copied, cd_br_index;
+  int cd_std;   // DecJob::dict_std: a compound copy may lie anywhere inside the dictionary
   // input position of win[0] (absolute bit position = (win_base + 2 ho) * 8 - 32 + bo)
   int64_t win_base;
   // the current metablock: header bit offset, output position, length (part checks)
@@ -1231,7 +1233,9 @@ __device__ int use_dictionary(DecS &s, int fence) {   // :903-983
   int address = s.distance - s.max_dist - 1 - s.cd_total;
   if (address < 0) {   // compound dictionary, one chunk (attachDictionaryChunk is called once)
     int a = -address - 1, length = s.copy_len;
-    if (s.cd_total > a + length) return ERR(s, -9);
+    // (the reference: the copy must reach the dictionary's end, and one that runs past it ends in
+    // copy_from_compound's TypeError; a prepared dictionary: it must stay inside, shared_dict.h)
+    if (s.cd_std ? !sd::copy_valid_u32((uint32_t)a, (uint32_t)length, (uint32_t)s.cd_total) : s.cd_total > a + length) return ERR(s, -9);
     s.dist_rb_idx = (s.dist_rb_idx + 1) & 3;
     s.rings[s.dist_rb_idx] = s.distance;
     s.mbl -= length;
@@ -2684,6 +2688,11 @@ __device__ __forceinline__ int decompress(DecS &s, int8_t *dist_extra, int32_t *
         if (s.pos >= fence) {
           s.next_running = ST_COPY_FROM_COMPOUND;
           s.running = ST_INIT_WRITE;
+          // The reference returns here, and its one-shot wrapper does not call again unless a
+          // whole output chunk came back: a copy from a customDictionary that reaches the ring's
+          // end ends the decoding there (the rest of a known size is zeros).  Kept for that
+          // path, byte for byte; a prepared dictionary's copy goes on behind the flush.
+          if (s.cd_std) continue;
           return 2;
         }
         s.running = ST_MAIN_LOOP;
@@ -2868,6 +2877,7 @@ __device__ void dec_init(DecS &s, const DecJob &job, uint8_t *ring, int32_t *tab
   s.rb_written = s.rb_ready = 0;
   s.cd = job.dict;
   s.cd_total = (int)job.dict_len;
+  s.cd_std = job.dict_std;
   s.cd_br_offset = s.cd_br_length = s.cd_br_copied = s.cd_br_index = 0;
   // iteration guard: far above what any stream can need (each iteration consumes input
   // bits or produces output), low enough that a bug cannot spin a GPU forever

@@ -106,6 +106,8 @@ struct Job {                // one stream (or streaming chunk) to encode
   uint32_t hq;              // quality >= 10 (context mode rule)
   uint32_t binary;          // set by context_mode_kernel: some metablock's literals are not UTF-8
                             // text (the parse's distance-cache candidates run there)
+  uint32_t cdict_std;       // 1: cdict is a prepared dictionary (mib_dictionary): copies from anywhere
+                            // in it (cdict_lookup_kernel), no tail copies (is_cdict_push)
 };
 
 // Per 64 KiB of global positions: where its stream's bytes are, so the match finder's gather
@@ -125,6 +127,14 @@ struct SegRef {
 // length; the parse turns it into d.  Downstream it is an ordinary copy: it pushes on the
 // distance ring and may be repeated by a short code, as in the decoder.
 constexpr uint32_t kCDictMark = 0xFFFFFFu;
+// A prepared dictionary (mib_dictionary, shared_dict.h) instead offers copies from anywhere
+// in it: its index is a table of 2^kHashBits buckets (keyed as the stream's positions are,
+// hashn over the mode's key bytes) of the kCDictWays highest dictionary addresses + 1 of each
+// bucket, highest first, 0 = empty.  A record of such a copy holds its real distance at that
+// position (beyond the window there), so every shorter length is a valid copy too and the
+// parse treats it as any match; only kCDictMark's exact-length rule does not apply.
+constexpr int kCDictWays = 8;
+static_assert(kLongCopy < (int)kMatchLenSat, "a dictionary copy is never saturated: the parse would extend it by reading the stream");
 
 // Static-dictionary references (RFC 7932 section 8, identity transform):
 // a copy whose distance exceeds the decoder's maximum backward distance names the word of
@@ -141,6 +151,16 @@ __device__ __forceinline__ uint32_t dict_hash(uint32_t w4) { return (w4 * 0x1E35
 
 // (only streams with dict set carry word references; at lgwin > 22 bit 23 is a distance bit)
 __device__ __forceinline__ bool is_word(const Job &jb, uint32_t d) { return jb.dict && is_dict(d); }
+// The decoder pushes the distance of a copy from the custom dictionary on its ring whatever
+// code the distance came with -- code 0 and the implicit last distance included
+// (use_dictionary, engine.ts:903-983) -- where a window copy at the last distance pushes
+// nothing.  With a prepared dictionary two copies in a row often have one distance (a run of
+// the dictionary below max backward: the window grows as the address does), so the kernels that
+// follow the decoder's ring (codes_kernel, raw_push_kernel, part_push_kernel) count that push:
+// `at` is the stream position of the copy, d its distance.
+__device__ __forceinline__ bool is_cdict_push(const Job &jb, uint32_t d, uint32_t at) {
+  return jb.cdict_std && !is_word(jb, d) && d > min(jb.win_abs + at, (1u << jb.lgwin) - 16);
+}
 
 struct Seg {
   uint32_t job, start, end;   // stream-local [start, end)
@@ -511,6 +531,9 @@ struct ItemMap {
 void launch_dict_matches(hipStream_t st, const Job *jobs, int njobs, uint32_t span, const uint32_t *dict_tab,
                          const uint8_t *dict_data, uint32_t *matches);
 void launch_cdict_matches(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, uint32_t *matches);
+void launch_cdict_index(hipStream_t st, const uint8_t *dict, uint32_t n, int hb, uint32_t *tab);
+void launch_cdict_lookup(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, const uint32_t *tab, int hb,
+                         uint32_t *matches);
 void launch_find_matches(hipStream_t st, const Job *jobs, const uint32_t *pos_job, const SegRef *seg_ref,
                          const uint32_t *skeys, const uint32_t *svals, uint32_t total, int depth, uint32_t max_dist,
                          bool hist, bool parts, uint32_t *matches);
@@ -560,7 +583,7 @@ void launch_stored(hipStream_t st, Job *jobs, int njobs, uint8_t *out);
 struct PushSum;
 void launch_ring_scan(hipStream_t st, Job *jobs, int njobs, Seg *segs, int nsegs, const RawCmd *raw, PushSum *push);
 void launch_part_index(hipStream_t st, const Job *jobs, int njobs, const Mb *mbs, const Seg *segs, int nsegs,
-                       const Cmd *cmds, const Unit *units, PushSum *push, uint8_t *out);
+                       const Cmd *cmds, const uint32_t *cmd_pos, const Unit *units, PushSum *push, uint8_t *out);
 size_t part_push_bytes();
 void launch_pack(hipStream_t st, const Job *jobs, int njobs, uint64_t out_pos, uint64_t out_cap, uint64_t *dst_off,
                  const uint8_t *src, uint8_t *dst);

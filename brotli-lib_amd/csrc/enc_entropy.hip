@@ -196,7 +196,16 @@ __global__ __launch_bounds__(NT) void codes_kernel(const Job *jobs, const Seg *s
     }
     // the decoder's distance ring before this command: pushes of the batch before it (by
     // rank), then the ring the batch started with
-    const uint32_t push = (q < nraw && !is_word(jb, d) && d != prevd) ? 1u : 0u;   // dictionary words never push
+    // (a prepared dictionary's copy pushes even when it repeats the last distance, see
+    // is_cdict_push: its position first, by a scan of the bytes alone; block-uniform)
+    bool cd_push = false;
+    if (jb.cdict_std) {
+      uint64_t ex0, tot0;
+      Scan(scan_tmp).ExclusiveSum((uint64_t)(ins + len), ex0, tot0);
+      cd_push = q < nraw && is_cdict_push(jb, d, sh_run + (uint32_t)ex0 + ins);
+      __syncthreads();
+    }
+    const uint32_t push = (q < nraw && !is_word(jb, d) && (d != prevd || cd_push)) ? 1u : 0u;   // dictionary words never push
     // one block scan of three packed counts, each field wide enough for its batch total (no
     // carries between fields): bytes, insert + copy, bits 35-63 (< 2^24 carried literals of
     // a <= 16 MiB metablock + the segment); literals, bits 10-34 (< 2^25); ring pushes, bits

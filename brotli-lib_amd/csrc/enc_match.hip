@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "enc_common.h"
+#include "shared_dict.h"
 
 namespace mib {
 namespace enc {
@@ -662,6 +663,69 @@ __global__ __launch_bounds__(256) void cdict_matches_kernel(const Job *jobs, con
 void launch_cdict_matches(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, uint32_t *matches) {
   const unsigned grid = (unsigned)std::min<uint64_t>(16384, (total + 255) / 256);
   hipLaunchKernelGGL(cdict_matches_kernel, dim3(grid), dim3(256), 0, st, jobs, pos_job, total, matches);
+}
+
+// ---------------------------------------------------------------- a prepared dictionary's copies
+// (kCDictWays, enc_common.h; the arithmetic: shared_dict.h.)  The index, once per handle: thread
+// per dictionary address a with hb bytes behind it.  Its bucket keeps the kCDictWays highest
+// addresses (+ 1), highest first: address a enters slot 0 by an atomic maximum and the smaller of
+// the two values moves on to the next slot.  Every slot keeps the maximum of what reaches it and
+// passes everything else on, so slot k ends up with the bucket's (k + 1)-th highest address
+// whatever the order of the threads.  (An address below the last slot's value is in no slot at
+// the end: it need not enter.)
+__global__ __launch_bounds__(256) void cdict_index_kernel(const uint8_t *dict, uint32_t n, int hb, uint32_t *tab) {
+  for (uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x; a + (uint32_t)hb <= n; a += (uint64_t)gridDim.x * 256) {
+    uint32_t *slot = tab + (size_t)hashn(dict + a, hb) * kCDictWays;
+    uint32_t v = (uint32_t)a + 1u;
+    if (__atomic_load_n(&slot[kCDictWays - 1], __ATOMIC_RELAXED) >= v) continue;
+    for (int k = 0; k < kCDictWays && v; k++) v = min(atomicMax(&slot[k], v), v);
+  }
+}
+// The lookup, after the window walk and the near scan: thread per stream position whose record is
+// still empty (dict_matches_kernel's rule).  The bucket of the position's key is walked, every
+// address measured forward against the dictionary (sd::measure: capped at the dictionary's end,
+// the parse segment's and the stream's end, and kLongCopy), and the longest copy of at least four
+// bytes (the nearest of equals) is stored with its real distance at this position.  An address
+// whose distance the record cannot hold (sd::record_holds) ends the walk: the rest lie farther.
+__global__ __launch_bounds__(256) void cdict_lookup_kernel(const Job *jobs, const uint32_t *pos_job, uint32_t total,
+                                                           const uint32_t *tab, int hb, uint32_t *matches) {
+  static_assert(sd::kMaxCopy == (uint32_t)kLongCopy, "shared_dict.h restates kLongCopy");
+  static_assert(sd::kRecordDistLimit == kCDictMark && sd::kRecordWordFlag == kDictFlag, "shared_dict.h restates the record's format");
+  for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < total; g += gridDim.x * 256) {
+    const Job &jb = jobs[pos_job[g >> kSegBits]];
+    if (!jb.cdict) continue;   // (a stored stream)
+    const uint32_t p = g - jb.pos_base;
+    if (p >= jb.n || jb.n - p < (uint32_t)hb) continue;
+    uint32_t *rec = matches + (uint64_t)g * kMatchRec;
+    if (rec[0] != 0) continue;   // the window has a match here
+    const uint32_t limit = min(((p >> kSegBits) + 1) << kSegBits, jb.n) - p;   // copies never cross a parse segment
+    const uint8_t *cur = jb.data + p;
+    const uint32_t window = min(jb.win_abs + p, (1u << jb.lgwin) - 16);
+    const uint32_t *slot = tab + (size_t)hashn(cur, hb) * kCDictWays;
+    uint32_t best = 3, bd = 0;
+    for (int k = 0; k < kCDictWays; k++) {
+      const uint32_t e = slot[k];
+      if (!e) break;
+      const uint64_t d = sd::distance_of(window, jb.cdict_len, e - 1u);
+      if (!sd::record_holds(d, jb.dict != 0)) break;
+      const uint32_t len = sd::measure(cur, limit, jb.cdict, jb.cdict_len, e - 1u);
+      if (len > best) {
+        best = len;
+        bd = (uint32_t)d;
+      }
+    }
+    if (bd) rec[0] = pack_match(bd, best);
+  }
+}
+void launch_cdict_index(hipStream_t st, const uint8_t *dict, uint32_t n, int hb, uint32_t *tab) {
+  if (n < (uint32_t)hb) return;
+  const unsigned grid = (unsigned)std::min<uint64_t>(16384, ((uint64_t)n + 255) / 256);
+  hipLaunchKernelGGL(cdict_index_kernel, dim3(grid), dim3(256), 0, st, dict, n, hb, tab);
+}
+void launch_cdict_lookup(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, const uint32_t *tab, int hb,
+                         uint32_t *matches) {
+  const unsigned grid = (unsigned)std::min<uint64_t>(16384, (total + 255) / 256);
+  hipLaunchKernelGGL(cdict_lookup_kernel, dim3(grid), dim3(256), 0, st, jobs, pos_job, total, tab, hb, matches);
 }
 
 void launch_find_matches(hipStream_t st, const Job *jobs, const uint32_t *pos_job, const SegRef *seg_ref,

@@ -16,7 +16,8 @@ struct PushSum {          // the explicit distances a segment pushes on the deco
 // Wave per segment: walk the commands back to front 64 at a time; a command pushes its
 // distance when it has a copy with an explicit distance code (code 0 = last distance and the
 // implicit-distance commands do not push: engine.ts distance ring update).
-__global__ __launch_bounds__(64) void part_push_kernel(const Job *jobs, const Seg *segs, const Cmd *cmds, PushSum *out) {
+__global__ __launch_bounds__(64) void part_push_kernel(const Job *jobs, const Seg *segs, const Cmd *cmds, const uint32_t *cmd_pos,
+                                                        PushSum *out) {
   const Seg &sg = segs[blockIdx.x];
   const Job &jb = jobs[sg.job];
   const int lane = threadIdx.x;
@@ -28,6 +29,7 @@ __global__ __launch_bounds__(64) void part_push_kernel(const Job *jobs, const Se
     return;
   }
   const Cmd *c = cmds + sg.cmd_off;
+  const uint32_t *cp = cmd_pos + sg.cmd_off;   // (the stream position of each command's insert)
   const uint32_t n = sg.ncmd + (sg.extra_ins ? 1 : 0);
   uint32_t got = 0, total = 0;
   for (int64_t hi = (int64_t)n; hi > 0; hi -= 64) {
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(64) void part_push_kernel(const Job *jobs, const Se
     uint32_t d = 0;
     if (q >= 0) {
       const Cmd cc = c[q];
-      push = cc.copy != 0 && (cc.dist_prefix & 0x3FF) != 0 && !is_word(jb, cc.dist);
+      push = cc.copy != 0 && (((cc.dist_prefix & 0x3FF) != 0 && !is_word(jb, cc.dist)) || is_cdict_push(jb, cc.dist, cp[q] + cc.ins));
       d = cc.dist;
     }
     uint64_t m = __ballot(push);
@@ -70,13 +72,36 @@ __global__ __launch_bounds__(64) void raw_push_kernel(const Job *jobs, const Seg
   const RawCmd *c = raw + sg.cmd_off;
   const int64_t n = sg.ncmd;
   uint32_t got = 0, total = 0;
+  // A prepared dictionary's copies push whatever their code (is_cdict_push), which goes by the
+  // copy's position: the commands start at sg.start (codes_kernel), so the position behind the
+  // last one is that plus every command's bytes, and each chunk of the walk ends where the one
+  // after it began.
+  const bool cds = jb.cdict_std != 0;
+  uint32_t chunk_end = 0;
+  if (cds) {
+    uint32_t bytes = 0;
+    for (int64_t q = lane; q < n; q += 64) bytes += c[q].ins + c[q].len;
+    for (int o = 32; o; o >>= 1) bytes += (uint32_t)__shfl_xor((int)bytes, o);
+    chunk_end = sg.start + bytes;
+  }
   for (int64_t hi = n; hi > 0; hi -= 64) {
     const int64_t q = hi - 64 + lane;
     bool push = false;
-    uint32_t d = 0;
+    uint32_t d = 0, span = 0, len = 0;
     if (q >= 0) {
       d = c[q].dist;
       push = !is_word(jb, d) && d != (q ? c[q - 1].dist : sg.prev_dist);
+      len = c[q].len;
+      span = c[q].ins + len;
+    }
+    if (cds) {
+      uint32_t suf = span;   // the bytes of this command and the chunk's later ones
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_down((int)suf, o);
+        suf += lane + o < 64 ? u : 0u;
+      }
+      if (q >= 0 && is_cdict_push(jb, d, chunk_end - suf + (span - len))) push = true;
+      chunk_end -= (uint32_t)__shfl((int)suf, 0);
     }
     uint64_t m = __ballot(push);
     total += (uint32_t)__popcll(m);
@@ -326,8 +351,8 @@ __global__ __launch_bounds__(kPiChunk) void part_index_kernel(const Job *jobs, i
 }
 
 void launch_part_index(hipStream_t st, const Job *jobs, int njobs, const Mb *mbs, const Seg *segs, int nsegs,
-                       const Cmd *cmds, const Unit *units, PushSum *push, uint8_t *out) {
-  hipLaunchKernelGGL(part_push_kernel, dim3(nsegs), dim3(64), 0, st, jobs, segs, cmds, push);
+                       const Cmd *cmds, const uint32_t *cmd_pos, const Unit *units, PushSum *push, uint8_t *out) {
+  hipLaunchKernelGGL(part_push_kernel, dim3(nsegs), dim3(64), 0, st, jobs, segs, cmds, cmd_pos, push);
   hipLaunchKernelGGL(part_index_kernel, dim3(njobs), dim3(kPiChunk), 0, st, jobs, njobs, mbs, segs, units, push, out);
 }
 

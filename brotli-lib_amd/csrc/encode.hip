@@ -31,9 +31,11 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <vector>
 
+#include "dictionary.h"
 #include "enc_common.h"
 
 extern "C" void mib_ctx_add_time(mib_ctx *c, const char *name, double ms);
@@ -174,6 +176,10 @@ struct StreamDesc {
   bool streaming;        // a BrotliEncoder chunk (part index whenever it has segments to split)
   const uint8_t *cdict;  // custom dictionary (device), or null
   uint32_t cdict_len, cdict_tail4;
+  // a prepared dictionary (mib_dictionary): copies from anywhere in it, found through its index
+  // for the call's key length (null: it has none, the dictionary is shorter than the key)
+  bool cdict_std;
+  const uint32_t *cdict_tab;
 };
 
 // Streams that get a part index (parts.h): one-shot streams of at least kPartMinStream bytes
@@ -369,7 +375,8 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
   // of earlier segments' 2^shift, so a multiple of 2^min_pshift, and its pieces follow it -- any
   // 2^min_pshift (or fewer, a power of two) pieces aligned at their count lie in one segment
   int min_pshift = kMaxPieceShift;
-  bool any_hist = false, any_parts = false, any_dict = false, any_cdict = false;
+  bool any_hist = false, any_parts = false, any_dict = false, any_cdict = false, cdict_std = false;
+  const uint32_t *cdict_tab = nullptr;
   for (size_t j = 0; j < k; j++) {
     Job &jb = jobs[j];
     memset(&jb, 0, sizeof(jb));
@@ -401,6 +408,8 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
       jb.cdict_len = sd[j].cdict_len;
       jb.cdict_tail4 = sd[j].cdict_tail4;
       any_cdict = true;
+      // (one dictionary a call: every stream that has one has the same)
+      if (sd[j].cdict_std) cdict_std = true, cdict_tab = sd[j].cdict_tab, jb.cdict_std = 1;
     }
     jb.dict = (!jb.uncompressed && jb.cdict_len < (1u << 22) && !sd[j].streaming && !sd[j].hist_tab && prm.quality >= 10 && prm.lgwin <= 22 &&
                dict_enabled()) ? 1 : 0;
@@ -603,8 +612,9 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
     launch_find_matches(st, d_jobs, d_seg_job, d_seg_ref, skeys, svals, total, depth, (1u << prm.lgwin) - 16, any_hist,
                         any_parts, matches);
     if (dd) launch_dict_matches(st, d_jobs, (int)k, dict_span(), dd->tab, dd->data, matches);
-    if (any_cdict) launch_cdict_matches(st, d_jobs, d_seg_job, total, matches);
+    if (any_cdict && !cdict_std) launch_cdict_matches(st, d_jobs, d_seg_job, total, matches);
     if (near_scan(prm)) launch_near_matches(st, d_jobs, d_seg_job, d_seg_ref, total, (1u << prm.lgwin) - 16, any_hist, any_parts, matches);
+    if (cdict_tab) launch_cdict_lookup(st, d_jobs, d_seg_job, total, cdict_tab, hash_bytes(prm), matches);
     if (!forked) {
       if (any_hist) launch_hist_update(st, d_jobs, d_seg_job, skeys, svals, total);
       launch_lit_histo(st, d_jobs, d_segs, nsegs, lit_h);
@@ -685,7 +695,7 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
     launch_emit(st, d_jobs, d_mbs, nmbs, d_segs, nsegs, cmds, cmd_pos, codes, units, tile_bits, trees, hdr, oscr);
     tm.stop();
     tm.start("part_index");
-    launch_part_index(st, d_jobs, (int)k, d_mbs, d_segs, nsegs, cmds, units, push, oscr);
+    launch_part_index(st, d_jobs, (int)k, d_mbs, d_segs, nsegs, cmds, cmd_pos, units, push, oscr);
     tm.stop();
   }
   tm.start("stored");
@@ -856,6 +866,8 @@ void fill_desc(StreamDesc &d, const uint8_t *p, uint64_t n, const Params &prm, b
   d.cdict = nullptr;
   d.cdict_len = 0;
   d.cdict_tail4 = 0;
+  d.cdict_std = false;
+  d.cdict_tab = nullptr;
   if (!one_shot) {
     d.hdr_lgwin = (uint32_t)prm.lgwin;
   } else if (n == 0) {
@@ -1005,7 +1017,8 @@ struct DefaultLock {   // the default context serves one host call at a time (ru
   ~DefaultLock() { mib_default_lock(0); }
 };
 
-static int encode_host(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out, int *status) {
+static int encode_host(const mib_span *in, size_t k, const mib_enc_opts *o, const mib_dictionary *dh, mib_buf *out,
+                       int *status) {
   DefaultLock use;
   mib_ctx *c = mib_default_ctx();
   if (!c) return MIB_E_NO_DEVICE;
@@ -1028,12 +1041,20 @@ static int encode_host(const mib_span *in, size_t k, const mib_enc_opts *o, mib_
   int rc = ctx_upload(c, st, up.data(), up.size());   // (through the context's pinned ring)
   if (rc) return rc;
   DevDict dd;
-  rc = o ? dd.upload(o->dict, o->dict_len, st) : 0;
+  rc = (o && !dh) ? dd.upload(o->dict, o->dict_len, st) : 0;
   if (rc) return rc;
+  if (dh && dh->device != mib_ctx_device_of(c)) return MIB_E_INVALID_ARG;
+  const int hb = hash_bytes(prm);
   std::vector<StreamDesc> sd(k);
   for (size_t i = 0; i < k; i++) {
     fill_desc(sd[i], d_in + ioff[i], in[i].size, prm, true);
     dd.attach(sd[i]);
+    if (dh) {   // a prepared dictionary: resident, with its index for this call's keys
+      sd[i].cdict = dh->d_data;
+      sd[i].cdict_len = (uint32_t)dh->n;
+      sd[i].cdict_std = true;
+      sd[i].cdict_tab = hb == 4 ? dh->tab4 : hb == 6 ? dh->tab6 : nullptr;
+    }
   }
   std::vector<uint64_t> ooff(k + 1, 0);
   rc = encode_streams(c, o, sd.data(), k, d_out, cap, ooff.data(), nullptr, st);
@@ -1182,7 +1203,7 @@ int mib_encode(const uint8_t *in, size_t n, const mib_enc_opts *o, mib_buf *out)
   out->size = 0;
   if (n >= (1ull << 31)) return MIB_E_INVALID_ARG;
   mib_span s{in, n};
-  return encode_host(&s, 1, o, out, nullptr);
+  return encode_host(&s, 1, o, nullptr, out, nullptr);
 }
 
 int mib_encode_batch(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out, int *status) {
@@ -1194,7 +1215,77 @@ int mib_encode_batch(const mib_span *in, size_t k, const mib_enc_opts *o, mib_bu
     if ((!in[i].data && in[i].size) || in[i].size >= (1ull << 31)) return MIB_E_INVALID_ARG;
   }
   if (!k) return 0;
-  return encode_host(in, k, o, out, status);
+  return encode_host(in, k, o, nullptr, out, status);
+}
+
+// ---------------------------------------------------------------- a prepared dictionary
+static void dictionary_release(mib_dictionary *d) {
+  for (void *p : {(void *)d->d_data, (void *)d->tab4, (void *)d->tab6})
+    if (p) hipFree(p);
+  delete d;
+}
+int mib_dictionary_new(const uint8_t *data, size_t n, mib_dictionary **out) {
+  if (!out) return MIB_E_INVALID_ARG;
+  *out = nullptr;
+  if ((!data && n) || n >= (1ull << 31)) return MIB_E_INVALID_ARG;
+  DefaultLock use;
+  mib_ctx *c = mib_default_ctx();
+  if (!c) return MIB_E_NO_DEVICE;
+  if (hipSetDevice(mib_ctx_device_of(c)) != hipSuccess) return MIB_E_NO_DEVICE;
+  hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
+  mib_dictionary *d = new (std::nothrow) mib_dictionary();
+  if (!d) return MIB_E_OUT_OF_MEMORY;
+  d->device = mib_ctx_device_of(c);
+  d->n = n;
+  const size_t tab_bytes = sizeof(uint32_t) * kCDictWays << kHashBits;
+  bool ok = hipMalloc(&d->d_data, n + mib_dictionary::kPad) == hipSuccess;
+  if (ok && n >= 4) ok = hipMalloc(&d->tab4, tab_bytes) == hipSuccess;
+  if (ok && n >= 6) ok = hipMalloc(&d->tab6, tab_bytes) == hipSuccess;
+  if (!ok) {
+    dictionary_release(d);
+    return MIB_E_OUT_OF_MEMORY;
+  }
+  // (the bytes behind the dictionary are zero: nothing compares them -- sd::measure stops at the
+  // dictionary's end -- and nothing that reads a few bytes past it sees another call's data)
+  ok = hipMemsetAsync(d->d_data + n, 0, mib_dictionary::kPad, st) == hipSuccess;
+  if (ok && n) {
+    const HostPiece up{d->d_data, data, n};
+    ok = ctx_upload(c, st, &up, 1) == 0;
+  }
+  for (int q = 0; ok && q < 2; q++) {
+    uint32_t *tab = q ? d->tab6 : d->tab4;
+    if (!tab) continue;
+    ok = hipMemsetAsync(tab, 0, tab_bytes, st) == hipSuccess;
+    launch_cdict_index(st, d->d_data, (uint32_t)n, q ? 6 : 4, tab);
+    ok = ok && hipGetLastError() == hipSuccess;
+  }
+  ok = hipStreamSynchronize(st) == hipSuccess && ok;
+  if (!ok) {
+    dictionary_release(d);
+    return MIB_E_NO_DEVICE;
+  }
+  *out = d;
+  return 0;
+}
+void mib_dictionary_free(mib_dictionary *d) {
+  if (!d) return;
+  DefaultLock use;   // (no call of the default context is using it)
+  hipSetDevice(d->device);
+  dictionary_release(d);
+}
+uint64_t mib_dictionary_size(const mib_dictionary *d) { return d ? d->n : 0; }
+
+int mib_encode_batch_dictionary(const mib_span *in, size_t k, const mib_enc_opts *o, const mib_dictionary *d, mib_buf *out,
+                                int *status) {
+  if (!d || (o && o->dict) || (k && (!in || !out || !status))) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++) {
+    out[i].data = nullptr;
+    out[i].size = 0;
+    status[i] = 0;
+    if ((!in[i].data && in[i].size) || in[i].size >= (1ull << 31)) return MIB_E_INVALID_ARG;
+  }
+  if (!k) return 0;
+  return encode_host(in, k, o, d, out, status);
 }
 
 // Diagnostic (tests): the candidate walk alone.  The batch is laid out as encode_group lays a

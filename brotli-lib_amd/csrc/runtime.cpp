@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "dictionary.h"
 #include "parts.h"
 #include "stream_session.h"
 #include "stream_batch.h"
@@ -972,6 +973,7 @@ struct PartStream {
   const PartPlan *plan;
   const uint8_t *dict;   // customDictionary (device), or null
   uint64_t dict_len;
+  int dict_std;          // DecJob::dict_std
 };
 static int decode_parts(mib_ctx *c, const std::vector<PartStream> &ps, std::vector<int> &ok, hipStream_t stream) {
   size_t nj = 0, ne = 0;
@@ -1016,6 +1018,7 @@ static int decode_parts(mib_ctx *c, const std::vector<PartStream> &ps, std::vect
       j.out_size = p.plan->total;
       j.dict = p.dict;
       j.dict_len = p.dict_len;
+      j.dict_std = p.dict_std;
       j.max_ring_log = p.plan->lgwin;
       j.part_entry = d_ent + e0 + i;
       j.next_entry = i + 1 < np ? d_ent + e0 + i + 1 : nullptr;
@@ -1120,7 +1123,7 @@ static int decode_streams(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_of
       part = plan_parts(f, jobs[i].in_len, plans[i]) && (uint64_t)plans[i].total + 64 <= jobs[i].out_cap;
     }
     if (part) {
-      ps.push_back(PartStream{jobs[i].in, jobs[i].in_len, jobs[i].out, &plans[i], nullptr, 0});
+      ps.push_back(PartStream{jobs[i].in, jobs[i].in_len, jobs[i].out, &plans[i], nullptr, 0, 0});
       ps_idx.push_back(i);
     } else {
       serial.push_back(jobs[i]);
@@ -1167,15 +1170,10 @@ int mib_ctx_decode_caps(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_offs
 }
 
 // one host stream through the device (brotliDecode semantics of decode.ts:18-65)
-int mib_decode(const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, int64_t max_out, int64_t exact_out,
-               mib_buf *out) {
-  if (!out || (!in && n)) return MIB_E_INVALID_ARG;
-  out->data = nullptr;
-  out->size = 0;
-  DefaultUse use;
-  mib_ctx *c = default_ctx();
-  if (!c) return MIB_E_NO_DEVICE;
-  hipSetDevice(c->device);
+// (dict: host bytes, staged here; or, dict_dev, a dictionary resident on the device, with
+// dict_std the rule its copies follow, DecJob::dict_std.  Caller: the default context held.)
+static int decode_one(mib_ctx *c, const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, const uint8_t *dict_dev,
+                      int dict_std, int64_t max_out, int64_t exact_out, mib_buf *out) {
   int64_t out_size = -1;
   if (exact_out >= 0) {
     out_size = exact_out;   // legacy numeric signature: no peek (decode.ts:27-44)
@@ -1197,6 +1195,10 @@ int mib_decode(const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, 
     const mib::HostPiece up[2] = {{d_in, in, n}, {d_dict, dict, dict ? dict_n : 0}};
     if ((rc = mib::ctx_upload(c, c->stream, up, dict ? 2 : 1))) return rc;
   }
+  if (dict_dev) {
+    d_dict = const_cast<uint8_t *>(dict_dev);   // (read only)
+    dict = dict_dev;                            // (below: "has a dictionary")
+  }
   if (exact_out < 0) {   // a stream with a part index: part-parallel, checked
     PartPlan plan;
     HostFetch f{in, n};
@@ -1206,7 +1208,7 @@ int mib_decode(const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, 
         (d_out = mib_ctx_stage(c, 1, (uint64_t)plan.total + 4096)) != nullptr) {
       std::vector<PartStream> ps(1);
       std::vector<int> ok;
-      ps[0] = PartStream{d_in, n, d_out, &plan, d_dict, dict ? dict_n : 0};
+      ps[0] = PartStream{d_in, n, d_out, &plan, d_dict, dict ? dict_n : 0, dict_std};
       rc = decode_parts(c, ps, ok, c->stream);
       if (rc == 0 && ok[0]) {
         return mib_buf_from_device(out, d_out, (uint64_t)plan.total);
@@ -1235,6 +1237,7 @@ int mib_decode(const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, 
     j.out_size = known ? out_size : -1;
     j.dict = d_dict;
     j.dict_len = dict ? dict_n : 0;
+    j.dict_std = dict_std;
     j.max_ring_log = peek_window_bits(in, n);
     rc = decode_jobs(c, jobs, c->stream);
     if (rc) break;
@@ -1255,6 +1258,121 @@ int mib_decode(const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, 
     break;
   }
   return rc;
+}
+
+int mib_decode(const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, int64_t max_out, int64_t exact_out,
+               mib_buf *out) {
+  if (!out || (!in && n)) return MIB_E_INVALID_ARG;
+  out->data = nullptr;
+  out->size = 0;
+  DefaultUse use;
+  mib_ctx *c = default_ctx();
+  if (!c) return MIB_E_NO_DEVICE;
+  hipSetDevice(c->device);
+  return decode_one(c, in, n, dict, dict_n, nullptr, 0, max_out, exact_out, out);
+}
+
+// mib_decode_batch with a prepared dictionary: the streams whose size is known (or guessed
+// right) in one launch, each with the dictionary and the standard rule; the streams with a part
+// index, and those that outgrew their slots, one by one through decode_one.
+constexpr int64_t kBatchSlotMax = 64ll << 20;
+int mib_decode_batch_dictionary(const mib_span *in, size_t k, const mib_dictionary *d, int64_t max_out, mib_buf *out,
+                                int *status) {
+  if (!d || max_out < -1 || (k && (!in || !out || !status))) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++) {
+    out[i].data = nullptr;
+    out[i].size = 0;
+    status[i] = 0;
+    if (!in[i].data && in[i].size) return MIB_E_INVALID_ARG;
+  }
+  if (!k) return 0;
+  DefaultUse use;
+  mib_ctx *c = default_ctx();
+  if (!c) return MIB_E_NO_DEVICE;
+  if (d->device != c->device) return MIB_E_INVALID_ARG;
+  hipSetDevice(c->device);
+  // 0: in the batch launch; 1: alone (a part index, a slot outgrown); 2: settled before decoding
+  std::vector<uint8_t> how(k, 0);
+  std::vector<int64_t> est(k, -1);
+  std::vector<uint64_t> ioff(k + 1, 0), ooff(k + 1, 0);
+  for (size_t i = 0; i < k; i++) {
+    ioff[i + 1] = ioff[i];
+    ooff[i + 1] = ooff[i];
+    est[i] = mib_decoded_size(in[i].data, in[i].size);
+    if (max_out >= 0 && est[i] > 0 && est[i] > max_out) {   // (mib_decode: the header's size, before decoding)
+      how[i] = 2;
+      status[i] = MIB_E_OUTPUT_LIMIT;
+      out[i].size = (size_t)est[i];
+      continue;
+    }
+    // (alone: a part index; and a stream whose header -- untrusted -- announces more than
+    // kBatchSlotMax, so that one stream's claim cannot make the shared buffers' allocation, and
+    // with it the whole call, fail: alone, a failed allocation is that slot's code)
+    if ((in[i].size >= 16 && looks_indexed(in[i].data, in[i].size)) || est[i] > kBatchSlotMax) {
+      how[i] = 1;
+      continue;
+    }
+    ioff[i + 1] = ioff[i] + ((in[i].size + 255) & ~(size_t)255);
+    const uint64_t cap = est[i] > 0 ? (uint64_t)est[i] : std::max<uint64_t>(1 << 16, 8 * (uint64_t)in[i].size);
+    ooff[i + 1] = ooff[i] + ((cap + MIB_IN_PLACE_SLACK + 64 + 255) & ~(uint64_t)255);
+  }
+  const bool any_batch = std::find(how.begin(), how.end(), 0) != how.end();
+  uint8_t *d_in = any_batch ? mib_ctx_stage(c, 0, ioff[k] + 16) : nullptr, *d_out = any_batch ? mib_ctx_stage(c, 1, ooff[k] + 64) : nullptr;
+  if (any_batch && (!d_in || !d_out)) return MIB_E_OUT_OF_MEMORY;
+  int rc = 0;
+  std::vector<mib::HostPiece> up;
+  std::vector<mib::DecJob> jobs;
+  std::vector<size_t> slot;
+  for (size_t i = 0; i < k; i++) {
+    if (how[i]) continue;
+    if (in[i].size) up.push_back(mib::HostPiece{d_in + ioff[i], in[i].data, in[i].size});
+    mib::DecJob j;
+    memset(&j, 0, sizeof(j));
+    j.in = d_in + ioff[i];
+    j.in_len = in[i].size;
+    j.out = d_out + ooff[i];
+    j.out_cap = ooff[i + 1] - ooff[i] - 64;
+    j.out_size = est[i] > 0 ? est[i] : -1;
+    j.dict = d->d_data;
+    j.dict_len = d->n;
+    j.dict_std = 1;
+    j.max_ring_log = peek_window_bits(in[i].data, in[i].size);
+    jobs.push_back(j);
+    slot.push_back(i);
+  }
+  if (!up.empty() && (rc = mib::ctx_upload(c, c->stream, up.data(), up.size()))) return rc;
+  if (!jobs.empty() && (rc = decode_jobs(c, jobs, c->stream))) return rc;
+  std::vector<mib_buf *> outs;
+  std::vector<const uint8_t *> src;
+  std::vector<uint64_t> lens;
+  for (size_t q = 0; q < jobs.size(); q++) {
+    const size_t i = slot[q];
+    status[i] = jobs[q].status;
+    if (jobs[q].status == MIB_E_NEED_SPACE) {
+      how[i] = 1;
+    } else if (jobs[q].status == 0) {
+      const uint64_t len = (uint64_t)jobs[q].result_len;
+      if (max_out >= 0 && (int64_t)len > max_out) {   // (the header can lie about the size)
+        status[i] = MIB_E_OUTPUT_LIMIT;
+        out[i].size = len;
+      } else {
+        outs.push_back(&out[i]);
+        src.push_back(d_out + ooff[i]);
+        lens.push_back(len);
+      }
+    }
+  }
+  if (!outs.empty() && (rc = mib_bufs_from_device(outs.size(), outs.data(), src.data(), lens.data()))) {
+    for (size_t i = 0; i < k; i++) mib_buf_free(&out[i]);
+    return rc;
+  }
+  // (the staging buffers are reused from here on)
+  for (size_t i = 0; i < k; i++)
+    if (how[i] == 1) {
+      status[i] = decode_one(c, in[i].data, in[i].size, nullptr, d->n, d->d_data, 1, max_out, -1, &out[i]);
+      if (status[i] != 0 && status[i] != MIB_E_OUTPUT_LIMIT) out[i].data = nullptr, out[i].size = 0;
+    }
+  return 0;
 }
 
 int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status) {

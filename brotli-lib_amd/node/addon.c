@@ -390,12 +390,166 @@ static napi_value decoder_batch(napi_env env, napi_callback_info info, int finis
 static napi_value js_decoder_update_batch(napi_env env, napi_callback_info info) { return decoder_batch(env, info, 0); }
 static napi_value js_decoder_finish_batch(napi_env env, napi_callback_info info) { return decoder_batch(env, info, 1); }
 
-/* encodeBatch([bytes...], quality, lgwin, mode, gpus, dictionary|null) -> [Buffer...]: one GPU
+/* ---- a prepared dictionary (mib_dictionary): dictionaryNew(bytes) -> external handle, freed by
+   dictionaryClose or, at the latest, when the handle is collected.  The box outlives the
+   mib_dictionary so that a closed handle is refused instead of read. */
+typedef struct { mib_dictionary *d; } DictBox;
+
+static void dictionary_finalize(napi_env env, void *data, void *hint) {
+  (void)env;
+  (void)hint;
+  DictBox *b = (DictBox *)data;
+  if (b->d) mib_dictionary_free(b->d);
+  free(b);
+}
+
+/* the handle of an argument: 0 and *d = NULL for null / undefined, 0 and the handle, or -1 with
+   an exception pending (not a handle, or closed) */
+static int get_dictionary(napi_env env, napi_value v, mib_dictionary **d) {
+  napi_valuetype t;
+  *d = NULL;
+  if (!v || napi_typeof(env, v, &t) != napi_ok || t == napi_null || t == napi_undefined) return 0;
+  void *h;
+  if (t != napi_external || napi_get_value_external(env, v, &h) != napi_ok) {
+    napi_throw_type_error(env, NULL, "dictionary must be a BrotliDictionary");
+    return -1;
+  }
+  if (!((DictBox *)h)->d) {
+    napi_throw_error(env, NULL, "the BrotliDictionary is closed");
+    return -1;
+  }
+  *d = ((DictBox *)h)->d;
+  return 0;
+}
+
+static napi_value js_dictionary_new(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  const uint8_t *p;
+  size_t n;
+  if (argc < 1 || get_bytes(env, argv[0], &p, &n)) {
+    napi_throw_type_error(env, NULL, "new BrotliDictionary(data: Uint8Array)");
+    return NULL;
+  }
+  DictBox *b = (DictBox *)calloc(1, sizeof(DictBox));
+  if (!b) return throw_code(env, MIB_E_OUT_OF_MEMORY);
+  int rc = mib_dictionary_new(p, n, &b->d);
+  if (rc) {
+    free(b);
+    return throw_code(env, rc);
+  }
+  if (napi_create_external(env, b, dictionary_finalize, NULL, &out) != napi_ok) {
+    dictionary_finalize(env, b, NULL);
+    napi_throw_error(env, NULL, "brotli_amd: N-API");
+    return NULL;
+  }
+  return out;
+}
+
+static napi_value js_dictionary_close(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void *h;
+  if (argc < 1 || napi_get_value_external(env, argv[0], &h) != napi_ok) {
+    napi_throw_type_error(env, NULL, "close()");
+    return NULL;
+  }
+  DictBox *b = (DictBox *)h;
+  if (b->d) mib_dictionary_free(b->d);
+  b->d = NULL;
+  return NULL;
+}
+
+static napi_value js_dictionary_size(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void *h;
+  if (argc < 1 || napi_get_value_external(env, argv[0], &h) != napi_ok) {
+    napi_throw_type_error(env, NULL, "size");
+    return NULL;
+  }
+  CHECK(env, napi_create_int64(env, (int64_t)mib_dictionary_size(((DictBox *)h)->d), &out));
+  return out;
+}
+
+/* a slot that failed: its Error (MIB_E_OUTPUT_LIMIT: err.size carries the offending size) */
+static napi_value slot_error(napi_env env, int code, size_t size) {
+  napi_value msg, err;
+  napi_create_string_utf8(env, code == MIB_E_OUTPUT_LIMIT ? "Decompressed size exceeds limit" : mib_strerror(code), NAPI_AUTO_LENGTH,
+                          &msg);
+  napi_create_error(env, NULL, msg, &err);
+  if (code == MIB_E_OUTPUT_LIMIT) {
+    napi_value sz;
+    napi_create_int64(env, (int64_t)size, &sz);
+    napi_set_named_property(env, err, "size", sz);
+  }
+  return err;
+}
+
+/* decodeBatchDictionary([bytes...], dictionary, maxOutputSize|-1) -> [Buffer | Error ...]:
+ * mib_decode_batch_dictionary, one result per slot */
+static napi_value js_decode_batch_dictionary(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  uint32_t k = 0;
+  bool is_arr = false;
+  mib_dictionary *d = NULL;
+  if (argc < 2 || napi_is_array(env, argv[0], &is_arr) != napi_ok || !is_arr) {
+    napi_throw_type_error(env, NULL, "decodeBatchDictionary(inputs: Uint8Array[], dictionary)");
+    return NULL;
+  }
+  if (get_dictionary(env, argv[1], &d)) return NULL;
+  CHECK(env, napi_get_array_length(env, argv[0], &k));
+  const int64_t max_out = argc > 2 ? get_i64(env, argv[2], -1) : -1;
+  mib_span *in = (mib_span *)calloc(k ? k : 1, sizeof(mib_span));
+  mib_buf *res = (mib_buf *)calloc(k ? k : 1, sizeof(mib_buf));
+  int *st = (int *)calloc(k ? k : 1, sizeof(int));
+  if (!in || !res || !st) {
+    free(in), free(res), free(st);
+    return throw_code(env, MIB_E_OUT_OF_MEMORY);
+  }
+  for (uint32_t i = 0; i < k; i++) {
+    napi_value e;
+    napi_get_element(env, argv[0], i, &e);
+    if (get_bytes(env, e, &in[i].data, &in[i].size)) {
+      free(in), free(res), free(st);
+      napi_throw_type_error(env, NULL, "every input must be a Uint8Array");
+      return NULL;
+    }
+  }
+  int rc = mib_decode_batch_dictionary(in, k, d, max_out, res, st);
+  free(in);
+  if (rc) {
+    free(res), free(st);
+    return throw_code(env, rc);
+  }
+  napi_create_array_with_length(env, k, &out);
+  for (uint32_t i = 0; i < k; i++) {
+    napi_value v;
+    if (st[i]) {
+      v = slot_error(env, st[i], res[i].size);
+      res[i].data = NULL;
+    } else {
+      v = take(env, &res[i]);
+      if (!v) break;
+    }
+    napi_set_element(env, out, i, v);
+  }
+  free(res);
+  free(st);
+  return out;
+}
+
+/* encodeBatch([bytes...], quality, lgwin, mode, gpus, customDictionary|null, dictionary|null) -> [Buffer...]: one GPU
  * launch sequence (gpus >= 0: sharded over that many GPUs, 0 = all; -1 / absent: the default
  * device) */
 static napi_value js_encode_batch(napi_env env, napi_callback_info info) {
-  size_t argc = 6;
-  napi_value argv[6], out;
+  size_t argc = 7;
+  napi_value argv[7], out;
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   uint32_t k = 0;
   bool is_arr = false;
@@ -412,6 +566,8 @@ static napi_value js_encode_batch(napi_env env, napi_callback_info info) {
   size_t dn = 0;
   if (argc > 5 && get_bytes(env, argv[5], &o.dict, &dn) == 0) o.dict_len = dn;
   else o.dict = NULL;
+  mib_dictionary *hd = NULL;   /* a BrotliDictionary: mib_encode_batch_dictionary */
+  if (argc > 6 && get_dictionary(env, argv[6], &hd)) return NULL;
   mib_span *in = (mib_span *)calloc(k ? k : 1, sizeof(mib_span));
   mib_buf *res = (mib_buf *)calloc(k ? k : 1, sizeof(mib_buf));
   int *st = (int *)calloc(k ? k : 1, sizeof(int));
@@ -425,7 +581,8 @@ static napi_value js_encode_batch(napi_env env, napi_callback_info info) {
     }
   }
   const int gpus = argc > 4 ? get_int(env, argv[4], -1) : -1;
-  int rc = gpus >= 0 ? mib_encode_batch_n(in, k, &o, gpus, res, st) : mib_encode_batch(in, k, &o, res, st);
+  int rc = hd ? mib_encode_batch_dictionary(in, k, &o, hd, res, st)
+              : gpus >= 0 ? mib_encode_batch_n(in, k, &o, gpus, res, st) : mib_encode_batch(in, k, &o, res, st);
   free(in);
   if (rc) {
     free(res), free(st);
@@ -455,6 +612,9 @@ typedef struct {
   mib_enc_opts o;
   uint8_t *blob;    /* the inputs, back to back (owned) */
   uint8_t *dict;    /* encode: the customDictionary (owned copy), or NULL */
+  mib_dictionary *hd;   /* a BrotliDictionary's handle, or NULL: the *_dictionary calls */
+  napi_ref hd_ref;      /* ... kept alive until the work has settled */
+  int64_t max_out;      /* decode with a handle: maxOutputSize, -1 none */
   mib_span *in;
   mib_buf *res;
   int *st;
@@ -467,7 +627,10 @@ static void async_free(AsyncBatch *a) {
 
 static void async_execute(napi_env env, void *data) {
   AsyncBatch *a = (AsyncBatch *)data;
-  if (a->gpus >= 0)
+  if (a->hd)
+    a->rc = a->decode ? mib_decode_batch_dictionary(a->in, a->k, a->hd, a->max_out, a->res, a->st)
+                      : mib_encode_batch_dictionary(a->in, a->k, &a->o, a->hd, a->res, a->st);
+  else if (a->gpus >= 0)
     a->rc = a->decode ? mib_decode_batch_n(a->in, a->k, a->gpus, a->res, a->st)
                       : mib_encode_batch_n(a->in, a->k, &a->o, a->gpus, a->res, a->st);
   else
@@ -482,9 +645,8 @@ static void async_complete(napi_env env, napi_status status, void *data) {
     for (uint32_t i = 0; i < a->k; i++) {
       napi_value v;
       if (a->st[i]) {   /* a stream that failed to decode: its Error, in its slot */
-        napi_value msg;
-        napi_create_string_utf8(env, mib_strerror(a->st[i]), NAPI_AUTO_LENGTH, &msg);
-        napi_create_error(env, NULL, msg, &v);
+        v = slot_error(env, a->st[i], a->res[i].size);
+        if (a->st[i] == MIB_E_OUTPUT_LIMIT) a->res[i].data = NULL;   /* (no data: the size alone) */
         mib_buf_free(&a->res[i]);
       } else {
         void *dst;
@@ -501,15 +663,16 @@ static void async_complete(napi_env env, napi_status status, void *data) {
     napi_reject_deferred(env, a->deferred, err);
     for (uint32_t i = 0; i < a->k; i++) mib_buf_free(&a->res[i]);
   }
+  if (a->hd_ref) napi_delete_reference(env, a->hd_ref);
   napi_delete_async_work(env, a->work);
   async_free(a);
 }
 
-/* encodeBatchAsync(inputs, quality, lgwin, mode, gpus, dictionary|null) /
- * decodeBatchAsync(inputs, gpus) -> Promise */
+/* encodeBatchAsync(inputs, quality, lgwin, mode, gpus, customDictionary|null, dictionary|null) /
+ * decodeBatchAsync(inputs, gpus, dictionary|null, maxOutputSize|-1) -> Promise */
 static napi_value start_async(napi_env env, napi_callback_info info, int decode) {
-  size_t argc = 6;
-  napi_value argv[6], promise, name;
+  size_t argc = 7;
+  napi_value argv[7], promise, name;
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   bool is_arr = false;
   uint32_t k = 0;
@@ -518,9 +681,14 @@ static napi_value start_async(napi_env env, napi_callback_info info, int decode)
     return NULL;
   }
   CHECK(env, napi_get_array_length(env, argv[0], &k));
+  const size_t hd_arg = decode ? 2 : 6;
+  mib_dictionary *hd = NULL;
+  if (argc > hd_arg && get_dictionary(env, argv[hd_arg], &hd)) return NULL;
   AsyncBatch *a = (AsyncBatch *)calloc(1, sizeof(AsyncBatch));
   a->k = k;
   a->decode = decode;
+  a->hd = hd;
+  a->max_out = decode && argc > 3 ? get_i64(env, argv[3], -1) : -1;
   a->gpus = decode ? (argc > 1 ? get_int(env, argv[1], -1) : -1) : (argc > 4 ? get_int(env, argv[4], -1) : -1);
   mib_enc_opts_default(&a->o);
   if (!decode) {
@@ -575,6 +743,13 @@ static napi_value start_async(napi_env env, napi_callback_info info, int decode)
         return throw_code(env, MIB_E_OUT_OF_MEMORY);
       }
     }
+  }
+  /* the handle's external stays referenced while the worker uses it (index.js also defers a
+     close() asked for meanwhile) */
+  if (hd && napi_create_reference(env, argv[hd_arg], 1, &a->hd_ref) != napi_ok) {
+    async_free(a);
+    napi_throw_error(env, NULL, "brotli_amd: N-API");
+    return NULL;
   }
   CHECK(env, napi_create_promise(env, &a->deferred, &promise));
   napi_create_string_utf8(env, decode ? "brotli_amd.decodeBatch" : "brotli_amd.encodeBatch", NAPI_AUTO_LENGTH, &name);
@@ -806,6 +981,10 @@ static napi_value init(napi_env env, napi_value exports) {
       {"decoderFinished", 0, js_decoder_finished, 0, 0, 0, napi_default, 0},
       {"decoderUpdateBatch", 0, js_decoder_update_batch, 0, 0, 0, napi_default, 0},
       {"decoderFinishBatch", 0, js_decoder_finish_batch, 0, 0, 0, napi_default, 0},
+      {"dictionaryNew", 0, js_dictionary_new, 0, 0, 0, napi_default, 0},
+      {"dictionaryClose", 0, js_dictionary_close, 0, 0, 0, napi_default, 0},
+      {"dictionarySize", 0, js_dictionary_size, 0, 0, 0, napi_default, 0},
+      {"decodeBatchDictionary", 0, js_decode_batch_dictionary, 0, 0, 0, napi_default, 0},
       {"encodeBatch", 0, js_encode_batch, 0, 0, 0, napi_default, 0},
       {"encodeBatchAsync", 0, js_encode_batch_async, 0, 0, 0, napi_default, 0},
       {"decodeBatchAsync", 0, js_decode_batch_async, 0, 0, 0, napi_default, 0},

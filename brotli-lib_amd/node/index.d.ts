@@ -9,6 +9,18 @@ export declare const EncoderMode: {
 }
 export type EncoderMode = (typeof EncoderMode)[keyof typeof EncoderMode]
 
+/** extension (brotli_amd.h mib_dictionary): shared bytes uploaded to the GPU and indexed there
+ *  once. Copies may come from anywhere in it (customDictionary: its tail only), so a stream
+ *  written with one decodes with one of the same bytes. Not for BrotliEncoder / BrotliDecoder. */
+export declare class BrotliDictionary {
+  constructor(data: Uint8Array | Int8Array)
+  /** the dictionary's length in bytes */
+  readonly size: number
+  readonly closed: boolean
+  /** frees the device memory; waits for pending async calls that use the dictionary */
+  close(): void
+}
+
 export interface BrotliEncodeOptions {
   /** 0..11, default 11 (clamped) */
   quality?: number
@@ -20,6 +32,9 @@ export interface BrotliEncodeOptions {
   /** extension: the encoder side of BrotliDecodeOptions.customDictionary; the stream decodes
    *  with (and only with) the same dictionary */
   customDictionary?: Uint8Array | Int8Array
+  /** extension: a prepared dictionary (not together with customDictionary, not with gpus; not
+   *  for BrotliEncoder) */
+  dictionary?: BrotliDictionary
 }
 
 export declare function brotliEncode(input: Uint8Array, options?: BrotliEncodeOptions): Uint8Array
@@ -35,6 +50,8 @@ export interface BrotliDecodeOptions {
   maxOutputSize?: number
   /** compound dictionary (engine.ts:142-159) */
   customDictionary?: Uint8Array | Int8Array
+  /** extension: the BrotliDictionary the stream was written with (not together with customDictionary) */
+  dictionary?: BrotliDictionary
 }
 
 /** options as a number: the legacy exact output size (truncate / zero-pad) */
@@ -74,7 +91,11 @@ export interface BatchOptions {
 export declare function brotliEncodeBatch(inputs: Uint8Array[], options?: BrotliEncodeOptions & BatchOptions): Uint8Array[]
 export declare function brotliEncodeBatchAsync(inputs: Uint8Array[], options?: BrotliEncodeOptions & BatchOptions): Promise<Uint8Array[]>
 /** a stream that fails to decode resolves to its Error in its slot */
-export declare function brotliDecodeBatchAsync(inputs: Uint8Array[], options?: BatchOptions): Promise<(Uint8Array | Error)[]>
+export declare function brotliDecodeBatchAsync(
+  inputs: Uint8Array[],
+  /** dictionary: the BrotliDictionary the streams were written with; maxOutputSize then applies to every stream */
+  options?: BatchOptions & { dictionary?: BrotliDictionary; maxOutputSize?: number },
+): Promise<(Uint8Array | Error)[]>
 /** many distinct BrotliDecoder sessions advance by one chunk each in shared GPU launches; per slot what decoder.update(chunk) alone would have returned, or the Error it would have thrown */
 export declare function brotliDecoderUpdateBatch(decoders: BrotliDecoder[], chunks: Uint8Array[]): (Uint8Array | Error)[]
 /** finish() of many BrotliDecoder sessions in shared launches; per slot the rest of the output, or the Error of an incomplete stream */

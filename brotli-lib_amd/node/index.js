@@ -38,8 +38,65 @@ function toU8(b) {
   return new Uint8Array(b.buffer, b.byteOffset, b.byteLength)
 }
 
+// BrotliDictionary (extension; brotli_amd.h mib_dictionary): shared bytes uploaded to the GPU and
+// indexed there once.  Pass it as options.dictionary to brotliEncode, brotliEncodeBatch,
+// brotliEncodeBatchAsync, brotliDecode and brotliDecodeBatchAsync.  Copies may come from anywhere
+// in it, so a stream written with one decodes with one of the same bytes (not with
+// customDictionary).  close() frees the device memory; while an async call that uses the
+// dictionary is pending, close() waits for it to settle.  size: the dictionary's length.
+class BrotliDictionary {
+  constructor(data) {
+    const d = data instanceof Uint8Array ? data : new Uint8Array(data.buffer, data.byteOffset, data.byteLength)
+    this._h = native.dictionaryNew(d)
+    this._size = d.length
+    this._pending = 0
+    this._closing = false
+  }
+  get size() {
+    return this._size
+  }
+  get closed() {
+    return this._h === null
+  }
+  close() {
+    if (this._h === null) return
+    if (this._pending > 0) {
+      this._closing = true
+      return
+    }
+    native.dictionaryClose(this._h)
+    this._h = null
+  }
+}
+// options.dictionary's handle (null: none); both kinds of dictionary at once is an error
+function handleOf(options) {
+  const d = options && options.dictionary
+  if (d === undefined || d === null) return null
+  if (!(d instanceof BrotliDictionary)) throw new TypeError('dictionary must be a BrotliDictionary')
+  if (options.customDictionary) throw new Error('dictionary and customDictionary exclude each other')
+  if (d._h === null || d._closing) throw new Error('the BrotliDictionary is closed')
+  return d
+}
+// an async call holds the dictionary until it settles
+function holding(d, promise) {
+  if (!d) return promise
+  d._pending++
+  const release = () => {
+    if (--d._pending === 0 && d._closing) {
+      d._closing = false
+      d.close()
+    }
+  }
+  return promise.then((v) => { release(); return v }, (e) => { release(); throw e })
+}
+function limitError(o, maxOutputSize) {
+  return o.size !== undefined ? new Error(`Decompressed size ${o.size} exceeds limit ${maxOutputSize}`) : o
+}
+
 function brotliEncode(input, options) {
   const [q, lg, m] = clampOptions(options)
+  const hd = handleOf(options)
+  if (hd) return toU8(native.encodeBatch([input], q, lg, m, -1, null, hd._h)[0])   // the batch with k = 1
   return toU8(native.encode(input, q, lg, m, dictOf(options)))
 }
 
@@ -69,6 +126,13 @@ function brotliDecode(buffer, options) {
   if (typeof options === 'number') {
     exact = options
   } else if (options) {
+    const hd = handleOf(options)
+    if (hd) {   // the batch with k = 1
+      const max = options.maxOutputSize
+      const r = native.decodeBatchDictionary([buffer], hd._h, max === undefined ? -1 : max)[0]
+      if (r instanceof Error) throw limitError(r, max)
+      return toU8(r)
+    }
     maxOutputSize = options.maxOutputSize
     const d = options.customDictionary
     if (d) dict = d instanceof Uint8Array ? d : new Uint8Array(d.buffer, d.byteOffset, d.byteLength)
@@ -139,17 +203,25 @@ function gpusOf(options) {
 // batch entry point of this engine: independent buffers in one GPU launch sequence
 function brotliEncodeBatch(inputs, options) {
   const [q, lg, m] = clampOptions(options)
-  return native.encodeBatch(inputs, q, lg, m, gpusOf(options), dictOf(options)).map(toU8)
+  const hd = handleOf(options)
+  return native.encodeBatch(inputs, q, lg, m, gpusOf(options), dictOf(options), hd ? hd._h : null).map(toU8)
 }
 
 // the same, off the JS thread: the GPU work runs on a worker (napi_async_work), a Promise
 // resolves to the outputs (decode: a stream that fails gives its Error in its slot)
 function brotliEncodeBatchAsync(inputs, options) {
   const [q, lg, m] = clampOptions(options)
-  return native.encodeBatchAsync(inputs, q, lg, m, gpusOf(options), dictOf(options)).then((outs) => outs.map(toU8))
+  const hd = handleOf(options)
+  return holding(hd, native.encodeBatchAsync(inputs, q, lg, m, gpusOf(options), dictOf(options), hd ? hd._h : null))
+    .then((outs) => outs.map(toU8))
 }
+// options.dictionary: the streams were written with that BrotliDictionary; options.maxOutputSize
+// then applies to every stream (its slot gets the Error)
 function brotliDecodeBatchAsync(inputs, options) {
-  return native.decodeBatchAsync(inputs, gpusOf(options)).then((outs) => outs.map((o) => (o instanceof Error ? o : toU8(o))))
+  const hd = handleOf(options)
+  const max = hd && options.maxOutputSize !== undefined ? options.maxOutputSize : -1
+  return holding(hd, native.decodeBatchAsync(inputs, gpusOf(options), hd ? hd._h : null, max))
+    .then((outs) => outs.map((o) => (o instanceof Error ? limitError(o, max) : toU8(o))))
 }
 
 // the FONT-mode caller's step before brotliEncode (reference README.md:63): the WOFF2
@@ -203,7 +275,7 @@ function woff2EncodeBatch(sfnts, options) {
 
 module.exports = {
   brotliEncode, BrotliEncoder, brotliDecode, BrotliDecoder, brotliDecodedSize, EncoderMode,
-  brotliEncodeBatch, brotliEncodeBatchAsync, brotliDecodeBatchAsync,
+  brotliEncodeBatch, brotliEncodeBatchAsync, brotliDecodeBatchAsync, BrotliDictionary,
   brotliDecoderUpdateBatch, brotliDecoderFinishBatch,
   woff2TransformGlyf, woff2TransformHmtx, woff2ReconstructGlyf, woff2ReconstructHmtx, woff2Decode, woff2DecodeBatch,
   woff2Encode, woff2EncodeBatch,

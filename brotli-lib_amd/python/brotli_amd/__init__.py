@@ -174,6 +174,15 @@ def _L():
                                          ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_decode_batch.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Buf),
                                          ctypes.POINTER(ctypes.c_int)]
+        lib.mib_dictionary_new.argtypes = [u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+        lib.mib_dictionary_free.argtypes = [ctypes.c_void_p]
+        lib.mib_dictionary_free.restype = None
+        lib.mib_dictionary_size.argtypes = [ctypes.c_void_p]
+        lib.mib_dictionary_size.restype = ctypes.c_uint64
+        lib.mib_encode_batch_dictionary.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
+                                                    ctypes.c_void_p, ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
+        lib.mib_decode_batch_dictionary.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int64,
+                                                    ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_encode_batch_n.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts), ctypes.c_int,
                                            ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_decode_batch_n.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_Buf),
@@ -314,7 +323,62 @@ def _bytes(x):
         return bytes(bytearray(x))
 
 
+class Dictionary:
+    """A prepared dictionary (mib_dictionary, brotli_amd.h): bytes that many small, similar
+    buffers are compressed against, uploaded and indexed on the GPU once.  Pass it as
+    `dictionary=` to encode_batch / decode_batch or as options['dictionary'] to brotliEncode /
+    brotliDecode.  Copies may come from anywhere in it, so a stream written with one decodes
+    only with one (of the same bytes).  close() frees the device memory; the object must stay
+    open while a call uses it.  len() is the dictionary's size."""
+
+    def __init__(self, data):
+        d = _bytes(data)
+        h = ctypes.c_void_p()
+        rc = _L().mib_dictionary_new(d, len(d), ctypes.byref(h))
+        if rc:
+            raise _err(rc)
+        self._h = h.value
+        self._n = len(d)
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def closed(self):
+        return self._h is None
+
+    def close(self):
+        if getattr(self, '_h', None):
+            _L().mib_dictionary_free(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # (interpreter shutdown)
+            pass
+
+
+def _dictionary(dictionary, options):
+    """the handle of a `dictionary` argument; both kinds of dictionary at once is an error"""
+    if not isinstance(dictionary, Dictionary):
+        raise TypeError('dictionary must be a brotli_amd.Dictionary')
+    if isinstance(options, dict) and options.get('customDictionary') is not None:
+        raise ValueError('dictionary and customDictionary exclude each other')
+    if dictionary.closed:
+        raise ValueError('the Dictionary is closed')
+    return dictionary._h
+
+
 def brotliEncode(input, options=None):
+    if options and options.get('dictionary') is not None:   # the batch with k = 1
+        return encode_batch([input], options, dictionary=options['dictionary'])[0]
     data, n, _keep = _in(input)
     buf = _Buf()
     rc = _L().mib_encode(data, n, ctypes.byref(_opts(options)), ctypes.byref(buf))
@@ -373,6 +437,11 @@ def brotliDecodedSize(data):
 
 def brotliDecode(buffer, options=None):
     """decode.ts:18-65: options = {'maxOutputSize', 'customDictionary'} or a legacy int size."""
+    if isinstance(options, dict) and options.get('dictionary') is not None:   # the batch with k = 1
+        r = decode_batch([buffer], dictionary=options['dictionary'], options=options)[0]
+        if isinstance(r, BrotliError):
+            raise r
+        return r
     data, n, _keep = _in(buffer)
     exact, max_out, dic = -1, -1, None
     if isinstance(options, int) and not isinstance(options, bool):
@@ -550,15 +619,21 @@ def debug_copy_batch(srcs, dsts, sizes):
         raise _err(rc)
 
 
-def encode_batch(buffers, options=None, gpus=None):
+def encode_batch(buffers, options=None, gpus=None, dictionary=None):
     """Encode independent buffers in one GPU launch sequence; returns list of bytes.  gpus:
-    shard the batch over that many GPUs (0: every visible one; mib_encode_batch_n)."""
+    shard the batch over that many GPUs (0: every visible one; mib_encode_batch_n).
+    dictionary: a Dictionary every buffer is compressed against (mib_encode_batch_dictionary;
+    not with gpus, not with options['customDictionary'])."""
     k = len(buffers)
     keep = [_in(b) for b in buffers]
     spans = (_Span * k)(*[_Span(_addr(a), n) for a, n, _ in keep])
     outs = (_Buf * k)()
     st = (ctypes.c_int * k)()
-    if gpus is None:
+    if dictionary is not None:
+        if gpus is not None:
+            raise ValueError('a Dictionary lives on one GPU: not with gpus')
+        rc = _L().mib_encode_batch_dictionary(spans, k, ctypes.byref(_opts(options)), _dictionary(dictionary, options), outs, st)
+    elif gpus is None:
         rc = _L().mib_encode_batch(spans, k, ctypes.byref(_opts(options)), outs, st)
     else:
         rc = _L().mib_encode_batch_n(spans, k, ctypes.byref(_opts(options)), int(gpus), outs, st)
@@ -624,14 +699,34 @@ def debug_prefix_codes(histograms):
     return res
 
 
-def decode_batch(buffers, gpus=None):
+def decode_batch(buffers, gpus=None, dictionary=None, options=None):
     """Decode independent streams on the GPU; returns a list of bytes or BrotliError.  gpus:
-    shard the batch over that many GPUs (0: every visible one; mib_decode_batch_n)."""
+    shard the batch over that many GPUs (0: every visible one; mib_decode_batch_n).
+    dictionary: the Dictionary the streams were written with (mib_decode_batch_dictionary; not
+    with gpus); with it options may hold 'maxOutputSize', which applies to every stream."""
     k = len(buffers)
     keep = [_in(b) for b in buffers]
     spans = (_Span * k)(*[_Span(_addr(a), n) for a, n, _ in keep])
     outs = (_Buf * k)()
     st = (ctypes.c_int * k)()
+    if dictionary is not None:
+        if gpus is not None:
+            raise ValueError('a Dictionary lives on one GPU: not with gpus')
+        max_out = -1
+        if isinstance(options, dict) and options.get('maxOutputSize') is not None:
+            max_out = int(options['maxOutputSize'])
+        rc = _L().mib_decode_batch_dictionary(spans, k, _dictionary(dictionary, options), max_out, outs, st)
+        if rc:
+            raise _err(rc)
+        res = []
+        for i in range(k):
+            if st[i] == -103:   # MIB_E_OUTPUT_LIMIT: brotliDecode's message
+                res.append(BrotliError('Decompressed size %d exceeds limit %d' % (outs[i].size, max_out), st[i]))
+            else:
+                res.append(_take(outs[i]) if st[i] == 0 else _err(st[i]))
+        return res
+    if options is not None:
+        raise ValueError('options apply to a call with a dictionary only')
     if gpus is None:
         rc = _L().mib_decode_batch(spans, k, outs, st)
     else:

@@ -209,6 +209,62 @@ int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status);
  * s % device count; results in input order.  Safe from several threads (calls serialise). */
 int mib_encode_batch_n(const mib_span *in, size_t k, const mib_enc_opts *o, int n_gpus, mib_buf *out, int *status);
 int mib_decode_batch_n(const mib_span *in, size_t k, int n_gpus, mib_buf *out, int *status);
+/* A prepared dictionary (extension; DESIGN.md 3d "A prepared dictionary"): shared bytes that many
+ * small, similar buffers are compressed against, uploaded once.  The handle lives on the default
+ * context's device: the bytes and, built there once by a kernel, an index of their positions
+ * (two tables of 4 MiB: 4-byte keys for FONT mode, 6-byte keys for GENERIC / TEXT; a table is
+ * left out where the dictionary is shorter than its key).  It is immutable, may be used by any
+ * number of calls and threads (the calls serialise on the default context, as every host entry
+ * point does) and must outlive the calls that use it.  n may be 0 .. 2^31 - 1; a dictionary of
+ * fewer than 4 bytes is attached (it shifts the addresses of the static dictionary's words, as
+ * any custom dictionary does) but offers no copies.
+ *   mib_dictionary_new   0; MIB_E_INVALID_ARG (NULL out, NULL data with n > 0, n >= 2^31: before
+ *                        any device work), MIB_E_NO_DEVICE, MIB_E_OUT_OF_MEMORY; on every error
+ *                        *out is NULL
+ *   mib_dictionary_free  NULL is harmless;  mib_dictionary_size: n, 0 for NULL
+ * Addressing ("standard"): the decoder's arithmetic is that of mib_decode's customDictionary,
+ * address = distance - max distance - 1 - n, a negative value a copy from dictionary offset
+ * a = -address - 1; but with a handle the copy is valid whenever a + length <= n (else -9), where
+ * mib_enc_opts.dict / customDictionary accept only the copy that ends at the dictionary's last
+ * byte.  So the encoder may copy from anywhere in the dictionary.  A stream written by the
+ * mib_enc_opts.dict path is valid under this rule too, and mib_decode_batch_dictionary reads it;
+ * a stream written with a handle generally decodes only through mib_decode_batch_dictionary
+ * (mib_decode answers -9 to its first copy from the middle of the dictionary).  To the author's
+ * knowledge this is how google/brotli's C decoder bounds a copy from an attached raw dictionary;
+ * no copy of that library was at hand, so interoperability with it is NOT verified.  One risk is
+ * known by name: this decoder (as the reference's) pushes the distance of a copy from the
+ * dictionary on its ring of last distances even when the distance came with code 0 or as a
+ * command's implicit last distance, and with a handle the encoder often writes such commands (a run
+ * of the dictionary cut into several copies repeats one distance) and codes what follows against
+ * that ring.  A decoder that leaves its ring unchanged on code 0 would read a later short distance
+ * code of such a stream differently.
+ * Encoder limits: a copy from the dictionary is at most 200 bytes (a longer run becomes several
+ * copies), and a match record holds a distance below 2^24 - 1 (below 2^23 where the stream also
+ * uses static-dictionary words: quality >= 10, lgwin <= 22, n < 2^22, where it always fits).  A
+ * copy from offset a at stream position p has the distance min(p, 2^lgwin - 16) + (n - a), so the
+ * encoder uses at least the last MIB_DICTIONARY_MATCH_SPAN(lgwin) bytes of the dictionary at every
+ * position, and at a position p below 2^lgwin - 16 that many more as p is below it; what lies in
+ * front of that is never copied from (the data still round-trips, as literals or window copies).
+ * The index keeps the 8 highest addresses of each of its 2^17 buckets, so of a dictionary of more
+ * than about a million bytes the front is found only where its keys are rare.  The decoder has no
+ * such limits.
+ * The batch calls return as mib_encode_batch / mib_decode_batch do, and MIB_E_INVALID_ARG also for
+ * a NULL handle, an o->dict set together with the handle, a NULL array with k > 0, NULL data with
+ * a size, max_out < -1 (before any device work); k == 0 needs no device.  status[i] / out[i] as
+ * mib_woff2_decode_batch's: everything about one stream is that slot's code and leaves the others
+ * running, a failed slot is {NULL, 0}.  max_out (-1: none) applies to every slot as mib_decode's
+ * does: MIB_E_OUTPUT_LIMIT, no data, the offending size in out[i].size.  Streams of fewer than 64
+ * bytes and quality 0 are stored, as without a dictionary.  BrotliEncoder / BrotliDecoder sessions,
+ * the mib_ctx_* and the _n calls take no handle. */
+typedef struct mib_dictionary mib_dictionary;
+#define MIB_DICTIONARY_MATCH_SPAN(lgwin) (0xFFFFFEu - ((1u << (lgwin)) - 16u))
+int mib_dictionary_new(const uint8_t *data, size_t n, mib_dictionary **out);
+void mib_dictionary_free(mib_dictionary *d);
+uint64_t mib_dictionary_size(const mib_dictionary *d);
+int mib_encode_batch_dictionary(const mib_span *in, size_t k, const mib_enc_opts *o, const mib_dictionary *d, mib_buf *out,
+                                int *status);
+int mib_decode_batch_dictionary(const mib_span *in, size_t k, const mib_dictionary *d, int64_t max_out, mib_buf *out,
+                                int *status);
 /* Visible HIP devices (0 without a GPU). */
 int mib_device_count(void);
 /* Diagnostics: the hardware property the match finder's bucket sort relies on for its
