@@ -26,6 +26,7 @@
 
 #include "../../include/brotli_amd.h"
 #include "common.h"
+#include "decode_plan.h"
 
 // runtime.cpp: result buffers (mib_set_allocator's allocator), the context's stream and staging
 extern "C" uint8_t *mib_buf_alloc(size_t n);
@@ -186,11 +187,8 @@ int decode_shard(Shard &sh, const mib_span *in, const std::vector<size_t> &idx, 
   std::vector<uint64_t> ioff, ooff(k + 1, 0);
   for (size_t q = 0; q < k; q++) {
     const mib_span &s = in[idx[q]];
-    const int64_t est = mib_decoded_size(s.data, s.size);
-    // a header size, else room for a part-indexed stream's total (known only from its index),
-    // else 8x the input; a stream that outgrows it is decoded again alone
-    const uint64_t capq = est > 0 ? (uint64_t)est : std::max<uint64_t>(1 << 16, 8 * (uint64_t)s.size);
-    ooff[q + 1] = ooff[q] + align256(capq + 4096);
+    // (decode_cap: a header size, else 8x the input; a stream that outgrows it is decoded again alone)
+    ooff[q + 1] = ooff[q] + align256(mib::decode_cap(mib_decoded_size(s.data, s.size), s.size) + 4096);
   }
   uint8_t *d_in = nullptr;
   int rc;

@@ -4,6 +4,9 @@
 // header peeks, buffer sizing, H2D/D2H copies.  Every byte of encode/decode compute runs in
 // the kernels (decode.hip, encode*.hip); with no gfx950 device the calls fail with
 // MIB_E_NO_DEVICE rather than falling back to the CPU.
+// What a one-shot decode works out from a stream's bytes alone (window bits, announced size, the
+// part index reader plan_parts, a host batch's slots) is decode_plan.h, which host tests run under
+// sanitizers; here: decode_jobs / decode_parts (a launch each), decode_one and decode_batch over them.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,11 +16,13 @@
 #include <mutex>
 #include <string>
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <thread>
 #include <vector>
 
 #include "common.h"
+#include "decode_plan.h"
 #include "dictionary.h"
 #include "parts.h"
 #include "stream_session.h"
@@ -143,148 +148,7 @@ int ensure_init() {
   return ensure_device(dev);
 }
 
-// decodeWindowBits (engine.ts:91-124) on the first bits of a stream: sizes the ring scratch
-int peek_window_bits(const uint8_t *b, size_t n) {
-  uint32_t v = 0;
-  for (size_t i = 0; i < 2 && i < n; i++) v |= (uint32_t)b[i] << (8 * i);
-  if ((v & 1) == 0) return 16;
-  int m = (v >> 1) & 7;
-  if (m) return 17 + m;
-  m = (v >> 4) & 7;
-  if (m == 1) return 24;   // large window: rejected by the decoder, any ring size will do
-  if (m) return 8 + m;
-  return 17;
-}
-
-// ---------------------------------------------------------------- part index (parts.h)
-// A stream's part plan: every valid entry of its index chain, in stream order.
-struct PartPlan {
-  std::vector<mib::PartEntry> ent;
-  int64_t total = -1;
-  int lgwin = 0;
-};
-
-// LSB-first bit reader over bytes fetched on demand (host memory or the device)
-template <class Fetch>
-struct HdrBits {
-  Fetch &fetch;
-  uint64_t bit;
-  bool ok = true;
-  uint32_t get(int n) {
-    uint32_t v = 0;
-    for (int i = 0; i < n; i++, bit++) {
-      int byte = 0;
-      if (!fetch(bit >> 3, 1, (uint8_t *)&byte)) {
-        ok = false;
-        return 0;
-      }
-      v |= (uint32_t)((byte >> (bit & 7)) & 1) << i;
-    }
-    return v;
-  }
-};
-
-// The index block at byte `at` (with the stream's window bits first when at == 0).
-// fetch(offset, length, dst) copies stream bytes; false past the end.
-// *end: the byte after the block's payload (where the decoder reads the next header).
-template <class Fetch>
-bool read_part_index(Fetch &fetch, uint64_t at, PartPlan &plan, uint64_t *next, uint64_t *end) {
-  HdrBits<Fetch> r{fetch, at * 8};
-  if (at == 0) {   // decodeWindowBits (engine.ts:91-124)
-    int lg;
-    if (r.get(1) == 0) lg = 16;
-    else {
-      const int m = (int)r.get(3);
-      if (m) lg = 17 + m;
-      else {
-        const int k = (int)r.get(3);
-        if (k == 1) return false;
-        lg = k ? 8 + k : 17;
-      }
-    }
-    plan.lgwin = lg;
-  }
-  if (r.get(1) != 0 || r.get(2) != 3 || r.get(1) != 0) return false;   // ISLAST 0, metadata, reserved 0
-  const int nb = (int)r.get(2);
-  if (nb == 0) return false;
-  const uint64_t len = (uint64_t)r.get(8 * nb) + 1;
-  if (!r.ok || len < sizeof(mib::PartHead)) return false;
-  const uint64_t pay = (r.bit + 7) >> 3;
-  mib::PartHead h;
-  if (!fetch(pay, sizeof(h), (uint8_t *)&h)) return false;
-  if (h.magic != mib::kPartMagic || h.version != 1 || h.entry_bytes != sizeof(mib::PartEntry)) return false;
-  if (sizeof(h) + (uint64_t)h.nentries * sizeof(mib::PartEntry) > len || h.nentries == 0 || h.nentries > (1u << 20)) return false;
-  if (at == 0 && (int)h.lgwin != plan.lgwin) return false;
-  std::vector<mib::PartEntry> e(h.nentries);
-  if (!fetch(pay + sizeof(h), sizeof(mib::PartEntry) * e.size(), (uint8_t *)e.data())) return false;
-  for (auto &x : e)
-    if (x.flags & mib::kPartValid) plan.ent.push_back(x);
-  plan.total = (int64_t)h.total;
-  *next = h.next_byte;
-  *end = pay + len;
-  return true;
-}
-
-// The whole chain of a stream of n bytes; false if it has none or it does not hold together.
-// Every part proves it ended exactly at the next entry's state, so the chain of parts is the
-// serial decode once its FIRST entry is: that entry must be the metablock header the
-// reference decoder reads right after skipping the first index block (its payload is opaque
-// to every decoder, so an entry pointing into it -- or anywhere else -- is not trusted).
-template <class Fetch>
-bool plan_parts(Fetch &fetch, uint64_t n, PartPlan &plan) {
-  uint64_t at = 0, next = 0, end = 0, first_end = 0;
-  for (int guard = 0; guard < (1 << 16); guard++) {
-    if (!read_part_index(fetch, at, plan, &next, &end)) {
-      if (at == 0) return false;
-      // BrotliEncoder.finish() with nothing pending adds only the final empty metablock
-      // (ISLAST, ISLASTEMPTY: one byte 0x03): the chain is complete
-      uint8_t b = 0;
-      if (n - at == 1 && fetch(at, 1, &b) && b == 0x03) next = 0;
-      break;
-    }
-    if (at == 0) first_end = end;
-    if (next == 0) break;
-    if (next <= at || next >= n) return false;
-    at = next;
-  }
-  if (next != 0) return false;   // the stream's total is only known from the final chunk's head
-  if (plan.ent.size() < 2 || plan.total <= 0 || plan.total > (1ll << 30)) return false;
-  if (plan.ent[0].pos != 0 || !(plan.ent[0].flags & mib::kPartAtMb)) return false;
-  if (plan.ent[0].bit != 8 * first_end || plan.ent[0].mb_bit != plan.ent[0].bit || plan.ent[0].mb_pos != 0) return false;
-  for (size_t i = 0; i < plan.ent.size(); i++) {
-    const mib::PartEntry &x = plan.ent[i];
-    if (x.bit >= 8 * n || x.mb_bit > x.bit || x.mb_pos > x.pos || x.pos >= (uint64_t)plan.total) return false;
-    if (i && (x.pos <= plan.ent[i - 1].pos || x.bit <= plan.ent[i - 1].bit)) return false;
-  }
-  return true;
-}
-
-struct HostFetch {   // stream bytes in host memory
-  const uint8_t *b;
-  uint64_t n;
-  bool operator()(uint64_t off, uint64_t len, uint8_t *dst) const {
-    if (off > n || len > n - off) return false;
-    memcpy(dst, b + off, len);
-    return true;
-  }
-};
-// The first 16 bytes of a stream: window bits then an index block with our magic?
-bool looks_indexed(const uint8_t *head, uint64_t n) {
-  HostFetch f{head, std::min<uint64_t>(n, 16)};
-  HdrBits<HostFetch> r{f, 0};
-  if (r.get(1) != 0) {
-    if (r.get(3) == 0 && r.get(3) == 1) return false;
-  }
-  if (r.get(1) != 0 || r.get(2) != 3 || r.get(1) != 0) return false;
-  const int nb = (int)r.get(2);
-  if (nb == 0) return false;
-  r.get(8 * nb);
-  const uint64_t pay = (r.bit + 7) >> 3;
-  uint32_t magic = 0;
-  return r.ok && f(pay, 4, (uint8_t *)&magic) && magic == mib::kPartMagic;
-}
-
-struct DeviceFetch {   // stream bytes on the device (small reads: index heads and entries)
+struct DeviceFetch {   // plan_parts' stream bytes on the device (small reads: index heads and entries)
   const uint8_t *d;
   uint64_t n;
   hipStream_t st;
@@ -614,9 +478,6 @@ int grow(void **p, uint64_t *cap, uint64_t need) {
   *cap = n;
   return 0;
 }
-namespace {
-}  // namespace
-
 extern "C" {
 
 void mib_enc_opts_default(mib_enc_opts *o) {
@@ -756,35 +617,7 @@ void mib_buf_free(mib_buf *b) {
   }
 }
 
-int64_t mib_decoded_size(const uint8_t *b, size_t n) {   // engine.ts:2155-2192 (header parse only)
-  size_t bp = 0;
-  auto rb = [&](int k) {
-    int v = 0;
-    for (int i = 0; i < k; i++, bp++) {
-      int byte = (bp >> 3) < n ? b[bp >> 3] : 0;
-      v |= ((byte >> (bp & 7)) & 1) << i;
-    }
-    return v;
-  };
-  if (rb(1)) {
-    int m = rb(3);
-    if (m == 0) {
-      int k = rb(3);
-      if (k == 1) {
-        if (rb(1)) return -1;
-        rb(6);
-      }
-    }
-  }
-  int last = rb(1);
-  if (last && rb(1)) return 0;
-  int nib = rb(2) + 4;
-  if (nib == 7) return -1;
-  int64_t mlen = 0;
-  for (int i = 0; i < nib; i++) mlen |= (int64_t)rb(4) << (i * 4);
-  mlen++;
-  return last ? mlen : -1;
-}
+int64_t mib_decoded_size(const uint8_t *b, size_t n) { return mib::decoded_size(b, n); }
 
 mib_ctx *mib_ctx_new(int device) {
   if (ensure_device(device) != 0) return nullptr;
@@ -913,20 +746,23 @@ int mib_ctx_kernel_times(mib_ctx *c, mib_kernel_time *out, int max) {
   return (int)c->times.size();
 }
 
-// decode k streams whose bytes are on the device; jobs[] describes them (host copy)
-static int decode_jobs(mib_ctx *c, std::vector<mib::DecJob> &jobs, hipStream_t stream) {
-  size_t k = jobs.size();
-  c->in_place_done = c->in_place_left = 0;
-  if (k == 0) return 0;
-  int max_log = 10;
-  for (auto &j : jobs) max_log = std::max(max_log, j.max_ring_log);
-  uint64_t ring_bytes = ((uint64_t)1 << max_log) + 37 + 256;
-  ring_bytes = (ring_bytes + 255) & ~(uint64_t)255;
-  uint64_t per_block = ring_bytes + mib::kDecodeScratchBytes;
-  per_block = (per_block + 255) & ~(uint64_t)255;
-  // (MIB_DEC_GRID: experiment knob, a smaller persistent grid -- fewer decoder waves per CU)
-  static const size_t grid_cap = mib::knob("MIB_DEC_GRID") ? (size_t)std::max(1, atoi(mib::knob("MIB_DEC_GRID"))) : 2048;
-  int grid = (int)std::min<size_t>(k, std::min<size_t>(grid_cap, 2048));
+// A zeroed job: input, output and its capacity, the size known beforehand (or -1), the window
+// bits that size the ring, and the stream's dictionary if it has one (dict_std: DecJob::dict_std)
+static mib::DecJob dec_job(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap, int64_t out_size, int lgwin,
+                           const uint8_t *dict = nullptr, uint64_t dict_len = 0, int dict_std = 0) {
+  mib::DecJob j;
+  memset(&j, 0, sizeof(mib::DecJob));
+  j.in = in, j.in_len = in_len, j.out = out, j.out_cap = out_cap, j.out_size = out_size, j.max_ring_log = lgwin;
+  j.dict = dict, j.dict_len = dict_len, j.dict_std = dict_std;
+  return j;
+}
+
+// One decode launch over jobs[] (not empty): scratch for `grid` blocks of per_block bytes, the
+// jobs to the device, launch() -- which finds them in c->d_jobs and its scratch in c->d_scratch --
+// timed under `name` when profiling, and the jobs back with what the kernel wrote into them.
+static int launch_jobs(mib_ctx *c, std::vector<mib::DecJob> &jobs, uint64_t per_block, int grid, const char *name,
+                       hipStream_t stream, const std::function<hipError_t()> &launch) {
+  const size_t k = jobs.size();
   int rc;
   c->scratch_trim.need = std::max(c->scratch_trim.need, per_block * (uint64_t)grid);
   if ((rc = grow((void **)&c->d_scratch, &c->scratch_bytes, per_block * (uint64_t)grid)) != 0) return rc;
@@ -944,18 +780,39 @@ static int decode_jobs(mib_ctx *c, std::vector<mib::DecJob> &jobs, hipStream_t s
     hipEventCreate(&e1);
     hipEventRecord(e0, stream);
   }
-  HIP_OK(mib_decode_launch(c->d_jobs, (int)k, c->d_scratch, per_block, ring_bytes, grid, waves_per_cu(c->device, (size_t)grid),
-                           stream));
+  HIP_OK(launch());
   if (c->profiling) hipEventRecord(e1, stream);
   HIP_OK(hipMemcpyAsync(jobs.data(), c->d_jobs, sizeof(mib::DecJob) * k, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
   if (c->profiling) {
     float ms = 0;
     hipEventElapsedTime(&ms, e0, e1);
-    c->add_time("decode_streams_kernel", ms);
+    c->add_time(name, ms);
     hipEventDestroy(e0);
     hipEventDestroy(e1);
   }
+  return 0;
+}
+
+// decode k streams whose bytes are on the device; jobs[] describes them (host copy)
+static int decode_jobs(mib_ctx *c, std::vector<mib::DecJob> &jobs, hipStream_t stream) {
+  size_t k = jobs.size();
+  c->in_place_done = c->in_place_left = 0;
+  if (k == 0) return 0;
+  int max_log = 10;
+  for (auto &j : jobs) max_log = std::max(max_log, j.max_ring_log);
+  uint64_t ring_bytes = ((uint64_t)1 << max_log) + 37 + 256;
+  ring_bytes = (ring_bytes + 255) & ~(uint64_t)255;
+  uint64_t per_block = ring_bytes + mib::kDecodeScratchBytes;
+  per_block = (per_block + 255) & ~(uint64_t)255;
+  // (MIB_DEC_GRID: experiment knob, a smaller persistent grid -- fewer decoder waves per CU)
+  static const size_t grid_cap = mib::knob("MIB_DEC_GRID") ? (size_t)std::max(1, atoi(mib::knob("MIB_DEC_GRID"))) : 2048;
+  int grid = (int)std::min<size_t>(k, std::min<size_t>(grid_cap, 2048));
+  const int rc = launch_jobs(c, jobs, per_block, grid, "decode_streams_kernel", stream, [&] {
+    return mib_decode_launch(c->d_jobs, (int)k, c->d_scratch, per_block, ring_bytes, grid, waves_per_cu(c->device, (size_t)grid),
+                             stream);
+  });
+  if (rc) return rc;
   for (auto &j : jobs) {
     c->in_place_done += j.in_place == 1 && j.status == 0;
     c->in_place_left += j.in_place == 2;
@@ -970,7 +827,7 @@ struct PartStream {
   const uint8_t *in;
   uint64_t in_len;
   uint8_t *out;
-  const PartPlan *plan;
+  const mib::PartPlan *plan;
   const uint8_t *dict;   // customDictionary (device), or null
   uint64_t dict_len;
   int dict_std;          // DecJob::dict_std
@@ -1009,17 +866,8 @@ static int decode_parts(mib_ctx *c, const std::vector<PartStream> &ps, std::vect
     }
     pos.push_back(p.plan->total);
     for (size_t i = 0; i < np; i++) {
-      mib::DecJob j;
-      memset(&j, 0, sizeof(j));
-      j.in = p.in;
-      j.in_len = p.in_len;
-      j.out = p.out;
-      j.out_cap = (uint64_t)p.plan->total;
-      j.out_size = p.plan->total;
-      j.dict = p.dict;
-      j.dict_len = p.dict_len;
-      j.dict_std = p.dict_std;
-      j.max_ring_log = p.plan->lgwin;
+      mib::DecJob j = dec_job(p.in, p.in_len, p.out, (uint64_t)p.plan->total, p.plan->total, p.plan->lgwin, p.dict,
+                              p.dict_len, p.dict_std);
       j.part_entry = d_ent + e0 + i;
       j.next_entry = i + 1 < np ? d_ent + e0 + i + 1 : nullptr;
       j.ppos = d_pos + p0;
@@ -1034,37 +882,14 @@ static int decode_parts(mib_ctx *c, const std::vector<PartStream> &ps, std::vect
   per_block = (per_block + 255) & ~(uint64_t)255;
   static const size_t grid_cap = mib::knob("MIB_PART_GRID") ? (size_t)std::max(1, atoi(mib::knob("MIB_PART_GRID"))) : 2048;
   const int grid = (int)std::min<size_t>(nj, grid_cap);
-  c->scratch_trim.need = std::max(c->scratch_trim.need, per_block * (uint64_t)grid);
-  if ((rc = grow((void **)&c->d_scratch, &c->scratch_bytes, per_block * (uint64_t)grid)) != 0) return rc;
-  if (nj > c->jobs_cap) {
-    if (c->d_jobs) hipFree(c->d_jobs);
-    c->d_jobs = nullptr;
-    c->jobs_cap = 0;
-    if (hipMalloc(&c->d_jobs, sizeof(mib::DecJob) * nj) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
-    c->jobs_cap = nj;
-  }
   HIP_OK(hipMemcpyAsync(d_ent, ents.data(), sizeof(mib::PartEntry) * ne, hipMemcpyHostToDevice, stream));
   HIP_OK(hipMemcpyAsync(d_pos, pos.data(), 8 * pos.size(), hipMemcpyHostToDevice, stream));
   HIP_OK(hipMemsetAsync(d_prog, 0, prog_b + 256, stream));   // progress words and the ticket
-  HIP_OK(hipMemcpyAsync(c->d_jobs, jobs.data(), sizeof(mib::DecJob) * nj, hipMemcpyHostToDevice, stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->profiling) {
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    hipEventRecord(e0, stream);
-  }
-  HIP_OK(mib_decode_parts_launch(c->d_jobs, (int)nj, c->d_scratch, per_block, d_ticket, grid,
-                                 waves_per_cu(c->device, (size_t)grid), stream));
-  if (c->profiling) hipEventRecord(e1, stream);
-  HIP_OK(hipMemcpyAsync(jobs.data(), c->d_jobs, sizeof(mib::DecJob) * nj, hipMemcpyDeviceToHost, stream));
-  HIP_OK(hipStreamSynchronize(stream));
-  if (c->profiling) {
-    float ms = 0;
-    hipEventElapsedTime(&ms, e0, e1);
-    c->add_time("decode_parts_kernel", ms);
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-  }
+  rc = launch_jobs(c, jobs, per_block, grid, "decode_parts_kernel", stream, [&] {
+    return mib_decode_parts_launch(c->d_jobs, (int)nj, c->d_scratch, per_block, d_ticket, grid,
+                                   waves_per_cu(c->device, (size_t)grid), stream);
+  });
+  if (rc) return rc;
   size_t q = 0;
   for (size_t i = 0; i < ps.size(); i++) {
     int good = 1;
@@ -1100,27 +925,22 @@ static int decode_streams(mib_ctx *c, const uint8_t *d_in, const uint64_t *in_of
     HIP_OK(hipStreamSynchronize(st));
   }
   for (size_t i = 0; i < k; i++) {
-    mib::DecJob &j = jobs[i];
-    memset(&j, 0, sizeof(j));
-    j.in = d_in + in_offsets[i];
-    j.in_len = in_offsets[i + 1] - in_offsets[i];
-    j.out = d_out + out_offsets[i];
-    j.out_cap = out_caps ? out_caps[i] : out_offsets[i + 1] - out_offsets[i];
-    j.out_size = -1;
-    j.max_ring_log = peek_window_bits(&heads[16 * i], (size_t)std::min<uint64_t>(j.in_len, 2));
+    const uint64_t n = in_offsets[i + 1] - in_offsets[i];
+    jobs[i] = dec_job(d_in + in_offsets[i], n, d_out + out_offsets[i], out_caps ? out_caps[i] : out_offsets[i + 1] - out_offsets[i],
+                      -1, mib::peek_window_bits(&heads[16 * i], (size_t)std::min<uint64_t>(n, 2)));
   }
   // streams with a part index decode part-parallel; the rest (and any part stream that does
   // not check out) one wave per stream
-  std::vector<PartPlan> plans(k);
+  std::vector<mib::PartPlan> plans(k);
   std::vector<PartStream> ps;
   std::vector<size_t> ps_idx;
   std::vector<mib::DecJob> serial;
   std::vector<size_t> serial_idx;
   for (size_t i = 0; i < k; i++) {
     bool part = false;
-    if (looks_indexed(&heads[16 * i], jobs[i].in_len)) {
+    if (mib::looks_indexed(&heads[16 * i], jobs[i].in_len)) {
       DeviceFetch f{jobs[i].in, jobs[i].in_len, st};
-      part = plan_parts(f, jobs[i].in_len, plans[i]) && (uint64_t)plans[i].total + 64 <= jobs[i].out_cap;
+      part = mib::plan_parts(f, jobs[i].in_len, plans[i]) && (uint64_t)plans[i].total + 64 <= jobs[i].out_cap;
     }
     if (part) {
       ps.push_back(PartStream{jobs[i].in, jobs[i].in_len, jobs[i].out, &plans[i], nullptr, 0, 0});
@@ -1200,11 +1020,11 @@ static int decode_one(mib_ctx *c, const uint8_t *in, size_t n, const uint8_t *di
     dict = dict_dev;                            // (below: "has a dictionary")
   }
   if (exact_out < 0) {   // a stream with a part index: part-parallel, checked
-    PartPlan plan;
-    HostFetch f{in, n};
+    mib::PartPlan plan;
+    mib::HostFetch f{in, n};
     // (the index is untrusted: a total beyond maxOutputSize, or one the device cannot hold,
     // just leaves the stream to the serial decoder, which finds out what it really is)
-    if (plan_parts(f, n, plan) && (max_out < 0 || plan.total <= max_out) &&
+    if (mib::plan_parts(f, n, plan) && (max_out < 0 || plan.total <= max_out) &&
         (d_out = mib_ctx_stage(c, 1, (uint64_t)plan.total + 4096)) != nullptr) {
       std::vector<PartStream> ps(1);
       std::vector<int> ok;
@@ -1228,17 +1048,9 @@ static int decode_one(mib_ctx *c, const uint8_t *in, size_t n, const uint8_t *di
       break;
     }
     std::vector<mib::DecJob> jobs(1);
-    mib::DecJob &j = jobs[0];
-    memset(&j, 0, sizeof(j));
-    j.in = d_in;
-    j.in_len = n;
-    j.out = d_out;
-    j.out_cap = known ? alloc : cap;   // unknown size: cap is the growth step's limit
-    j.out_size = known ? out_size : -1;
-    j.dict = d_dict;
-    j.dict_len = dict ? dict_n : 0;
-    j.dict_std = dict_std;
-    j.max_ring_log = peek_window_bits(in, n);
+    // (unknown size: cap is the growth step's limit)
+    jobs[0] = dec_job(d_in, n, d_out, known ? alloc : cap, known ? out_size : -1, mib::peek_window_bits(in, n), d_dict,
+                      dict ? dict_n : 0, dict_std);
     rc = decode_jobs(c, jobs, c->stream);
     if (rc) break;
     rc = jobs[0].status;
@@ -1272,84 +1084,60 @@ int mib_decode(const uint8_t *in, size_t n, const uint8_t *dict, size_t dict_n, 
   return decode_one(c, in, n, dict, dict_n, nullptr, 0, max_out, exact_out, out);
 }
 
-// mib_decode_batch with a prepared dictionary: the streams whose size is known (or guessed
-// right) in one launch, each with the dictionary and the standard rule; the streams with a part
-// index, and those that outgrew their slots, one by one through decode_one.
-constexpr int64_t kBatchSlotMax = 64ll << 20;
-int mib_decode_batch_dictionary(const mib_span *in, size_t k, const mib_dictionary *d, int64_t max_out, mib_buf *out,
-                                int *status) {
-  if (!d || max_out < -1 || (k && (!in || !out || !status))) return MIB_E_INVALID_ARG;
-  for (size_t i = 0; i < k; i++) {
-    out[i].data = nullptr;
-    out[i].size = 0;
-    status[i] = 0;
-    if (!in[i].data && in[i].size) return MIB_E_INVALID_ARG;
-  }
-  if (!k) return 0;
+// The body of mib_decode_batch (d null, max_out -1) and mib_decode_batch_dictionary: the streams in
+// one launch, each in a slot sized by what its header announces (or guessed: decode_plan.h
+// plan_batch), with the dictionary and the standard rule if there is one; the streams that outgrew
+// their slots, and those the alone rules single out, one by one through decode_one.
+static int decode_batch(const mib_span *in, size_t k, const mib_dictionary *d, int64_t max_out, mib_buf *out, int *status) {
+  static const bool timing = mib::knob("MIB_HOST_TIMING") != nullptr;
+  const auto t_in = std::chrono::steady_clock::now();
+  auto ms_since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count(); };
   DefaultUse use;
   mib_ctx *c = default_ctx();
   if (!c) return MIB_E_NO_DEVICE;
-  if (d->device != c->device) return MIB_E_INVALID_ARG;
+  if (d && d->device != c->device) return MIB_E_INVALID_ARG;
   hipSetDevice(c->device);
-  // 0: in the batch launch; 1: alone (a part index, a slot outgrown); 2: settled before decoding
-  std::vector<uint8_t> how(k, 0);
-  std::vector<int64_t> est(k, -1);
-  std::vector<uint64_t> ioff(k + 1, 0), ooff(k + 1, 0);
-  for (size_t i = 0; i < k; i++) {
-    ioff[i + 1] = ioff[i];
-    ooff[i + 1] = ooff[i];
-    est[i] = mib_decoded_size(in[i].data, in[i].size);
-    if (max_out >= 0 && est[i] > 0 && est[i] > max_out) {   // (mib_decode: the header's size, before decoding)
-      how[i] = 2;
-      status[i] = MIB_E_OUTPUT_LIMIT;
-      out[i].size = (size_t)est[i];
-      continue;
-    }
-    // (alone: a part index; and a stream whose header -- untrusted -- announces more than
-    // kBatchSlotMax, so that one stream's claim cannot make the shared buffers' allocation, and
-    // with it the whole call, fail: alone, a failed allocation is that slot's code)
-    if ((in[i].size >= 16 && looks_indexed(in[i].data, in[i].size)) || est[i] > kBatchSlotMax) {
-      how[i] = 1;
-      continue;
-    }
-    ioff[i + 1] = ioff[i] + ((in[i].size + 255) & ~(size_t)255);
-    const uint64_t cap = est[i] > 0 ? (uint64_t)est[i] : std::max<uint64_t>(1 << 16, 8 * (uint64_t)in[i].size);
-    ooff[i + 1] = ooff[i] + ((cap + MIB_IN_PLACE_SLACK + 64 + 255) & ~(uint64_t)255);
-  }
-  const bool any_batch = std::find(how.begin(), how.end(), 0) != how.end();
-  uint8_t *d_in = any_batch ? mib_ctx_stage(c, 0, ioff[k] + 16) : nullptr, *d_out = any_batch ? mib_ctx_stage(c, 1, ooff[k] + 64) : nullptr;
-  if (any_batch && (!d_in || !d_out)) return MIB_E_OUT_OF_MEMORY;
-  int rc = 0;
+  // The two calls differ in routing, and only here.  With a dictionary handle a part-indexed stream
+  // goes alone, and so decodes part-parallel (decode_one), as does a stream whose header announces
+  // more than kBatchSlotMax; without one both stay in the launch, the indexed stream on one wave, the
+  // announced size uncapped.  (Whether the plain call should adopt either rule has not been measured.)
+  const bool alone_rules = d != nullptr;
+  const mib::BatchLayout lay = mib::plan_batch(in, k, max_out, alone_rules);
+  std::vector<uint8_t> alone(k, 0);
   std::vector<mib::HostPiece> up;
   std::vector<mib::DecJob> jobs;
   std::vector<size_t> slot;
   for (size_t i = 0; i < k; i++) {
-    if (how[i]) continue;
-    if (in[i].size) up.push_back(mib::HostPiece{d_in + ioff[i], in[i].data, in[i].size});
-    mib::DecJob j;
-    memset(&j, 0, sizeof(j));
-    j.in = d_in + ioff[i];
-    j.in_len = in[i].size;
-    j.out = d_out + ooff[i];
-    j.out_cap = ooff[i + 1] - ooff[i] - 64;
-    j.out_size = est[i] > 0 ? est[i] : -1;
-    j.dict = d->d_data;
-    j.dict_len = d->n;
-    j.dict_std = 1;
-    j.max_ring_log = peek_window_bits(in[i].data, in[i].size);
-    jobs.push_back(j);
-    slot.push_back(i);
+    const mib::BatchItem &t = lay.item[i];
+    alone[i] = t.how == mib::kAlone;
+    if (t.how == mib::kInLaunch) slot.push_back(i);
+    if (t.how == mib::kSettled) status[i] = MIB_E_OUTPUT_LIMIT, out[i].size = (size_t)t.est;
   }
+  uint8_t *d_in = nullptr, *d_out = nullptr;
+  if (!slot.empty()) {
+    d_in = mib_ctx_stage(c, 0, lay.in_bytes + 16), d_out = mib_ctx_stage(c, 1, lay.out_bytes + 64);
+    if (!d_in || !d_out) return MIB_E_OUT_OF_MEMORY;
+  }
+  up.reserve(slot.size()), jobs.reserve(slot.size());
+  for (size_t i : slot) {   // exact input lengths, padded slots
+    const mib::BatchItem &t = lay.item[i];
+    if (in[i].size) up.push_back(mib::HostPiece{d_in + t.in_off, in[i].data, in[i].size});
+    jobs.push_back(dec_job(d_in + t.in_off, in[i].size, d_out + t.out_off, t.out_slot - 64, t.est > 0 ? t.est : -1,
+                           mib::peek_window_bits(in[i].data, in[i].size), d ? d->d_data : nullptr, d ? d->n : 0, d ? 1 : 0));
+  }
+  int rc = 0;
   if (!up.empty() && (rc = mib::ctx_upload(c, c->stream, up.data(), up.size()))) return rc;
-  if (!jobs.empty() && (rc = decode_jobs(c, jobs, c->stream))) return rc;
+  const double t_up = timing ? ms_since() : 0.0;
+  if (!jobs.empty()) rc = decode_jobs(c, jobs, c->stream);
+  const double t_dec = timing ? ms_since() : 0.0;
   std::vector<mib_buf *> outs;
   std::vector<const uint8_t *> src;
   std::vector<uint64_t> lens;
-  for (size_t q = 0; q < jobs.size(); q++) {
+  for (size_t q = 0; q < jobs.size() && rc == 0; q++) {
     const size_t i = slot[q];
     status[i] = jobs[q].status;
     if (jobs[q].status == MIB_E_NEED_SPACE) {
-      how[i] = 1;
+      alone[i] = 1;
     } else if (jobs[q].status == 0) {
       const uint64_t len = (uint64_t)jobs[q].result_len;
       if (max_out >= 0 && (int64_t)len > max_out) {   // (the header can lie about the size)
@@ -1357,88 +1145,45 @@ int mib_decode_batch_dictionary(const mib_span *in, size_t k, const mib_dictiona
         out[i].size = len;
       } else {
         outs.push_back(&out[i]);
-        src.push_back(d_out + ooff[i]);
+        src.push_back(d_out + lay.item[i].out_off);
         lens.push_back(len);
       }
     }
   }
-  if (!outs.empty() && (rc = mib_bufs_from_device(outs.size(), outs.data(), src.data(), lens.data()))) {
+  if (!outs.empty() && (rc = mib_bufs_from_device(outs.size(), outs.data(), src.data(), lens.data())))
     for (size_t i = 0; i < k; i++) mib_buf_free(&out[i]);
-    return rc;
-  }
-  // (the staging buffers are reused from here on)
-  for (size_t i = 0; i < k; i++)
-    if (how[i] == 1) {
-      status[i] = decode_one(c, in[i].data, in[i].size, nullptr, d->n, d->d_data, 1, max_out, -1, &out[i]);
+  // (the staging buffers are reused from here on: the growing single-stream path)
+  for (size_t i = 0; i < k && rc == 0; i++)
+    if (alone[i]) {
+      status[i] = decode_one(c, in[i].data, in[i].size, nullptr, d ? d->n : 0, d ? d->d_data : nullptr, d ? 1 : 0, max_out, -1,
+                             &out[i]);
       if (status[i] != 0 && status[i] != MIB_E_OUTPUT_LIMIT) out[i].data = nullptr, out[i].size = 0;
     }
-  return 0;
-}
-
-int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status) {
-  static const bool timing = mib::knob("MIB_HOST_TIMING") != nullptr;
-  const auto t_in = std::chrono::steady_clock::now();
-  auto ms_since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count(); };
-  DefaultUse use;
-  mib_ctx *c = default_ctx();
-  if (!c) return MIB_E_NO_DEVICE;
-  hipSetDevice(c->device);
-  std::vector<uint64_t> ioff(k + 1, 0), ooff(k + 1, 0);
-  for (size_t i = 0; i < k; i++) {
-    ioff[i + 1] = ioff[i] + ((in[i].size + 255) & ~(size_t)255);
-    int64_t est = mib_decoded_size(in[i].data, in[i].size);
-    uint64_t cap = est > 0 ? (uint64_t)est : std::max<uint64_t>(1 << 16, 8 * (uint64_t)in[i].size);
-    // (+ the slack that lets a one-metablock stream decode in its slot, + the 64 behind every slot)
-    ooff[i + 1] = ooff[i] + ((cap + MIB_IN_PLACE_SLACK + 64 + 255) & ~(uint64_t)255);
-  }
-  uint8_t *d_in = mib_ctx_stage(c, 0, ioff[k] + 16), *d_out = mib_ctx_stage(c, 1, ooff[k] + 64);
-  if (!d_in || !d_out) return MIB_E_OUT_OF_MEMORY;
-  int rc = 0;
-  {
-    std::vector<mib::HostPiece> up;
-    for (size_t i = 0; i < k; i++)
-      if (in[i].size) up.push_back(mib::HostPiece{d_in + ioff[i], in[i].data, in[i].size});
-    if ((rc = mib::ctx_upload(c, c->stream, up.data(), up.size()))) return rc;
-  }
-  for (size_t i = 0; i < k; i++) out[i].data = nullptr, out[i].size = 0;
-  // exact input lengths, padded slots
-  std::vector<mib::DecJob> jobs(k);
-  for (size_t i = 0; i < k; i++) {
-    mib::DecJob &j = jobs[i];
-    memset(&j, 0, sizeof(j));
-    j.in = d_in + ioff[i];
-    j.in_len = in[i].size;
-    j.out = d_out + ooff[i];
-    j.out_cap = ooff[i + 1] - ooff[i] - 64;
-    int64_t est = mib_decoded_size(in[i].data, in[i].size);
-    j.out_size = est > 0 ? est : -1;
-    j.max_ring_log = peek_window_bits(in[i].data, in[i].size);
-  }
-  const double t_up = timing ? ms_since() : 0.0;
-  rc = decode_jobs(c, jobs, c->stream);
-  const double t_dec = timing ? ms_since() : 0.0;
-  if (rc == 0) {
-    std::vector<mib_buf *> outs;
-    std::vector<const uint8_t *> src;
-    std::vector<uint64_t> lens;
-    for (size_t i = 0; i < k; i++) {
-      status[i] = jobs[i].status;
-      if (jobs[i].status == 0) {
-        outs.push_back(&out[i]);
-        src.push_back(d_out + ooff[i]);
-        lens.push_back((uint64_t)jobs[i].result_len);
-      }
-    }
-    if ((rc = mib_bufs_from_device(outs.size(), outs.data(), src.data(), lens.data()))) return rc;
-    // then (the staging buffers are reused) the streams that outgrew their slots, alone
-    // through the growing single-stream path
-    for (size_t i = 0; i < k; i++)
-      if (jobs[i].status == MIB_E_NEED_SPACE) status[i] = mib_decode(in[i].data, in[i].size, nullptr, 0, -1, -1, &out[i]);
-  }
   if (timing)
     fprintf(stderr, "[mib] decode_batch %zu streams: upload done %.2f ms, decode done %.2f, results %.2f\n", k, t_up, t_dec,
             ms_since());
   return rc;
+}
+
+// what both batch calls ask of their arguments; clears out[] and status[]
+static int batch_args(const mib_span *in, size_t k, mib_buf *out, int *status) {
+  if (k && (!in || !out || !status)) return MIB_E_INVALID_ARG;
+  for (size_t i = 0; i < k; i++) {
+    out[i].data = nullptr, out[i].size = 0, status[i] = 0;
+    if (!in[i].data && in[i].size) return MIB_E_INVALID_ARG;
+  }
+  return 0;
+}
+
+int mib_decode_batch_dictionary(const mib_span *in, size_t k, const mib_dictionary *d, int64_t max_out, mib_buf *out,
+                                int *status) {
+  if (!d || max_out < -1 || batch_args(in, k, out, status)) return MIB_E_INVALID_ARG;
+  return k ? decode_batch(in, k, d, max_out, out, status) : 0;
+}
+
+int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status) {
+  if (batch_args(in, k, out, status)) return MIB_E_INVALID_ARG;
+  return k ? decode_batch(in, k, nullptr, -1, out, status) : 0;
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 """Reader of the part index (brotli-lib_amd/csrc/parts.h) a stream carries in its first
-metadata metablock(s): test infrastructure, independent of the C++ reader in runtime.cpp."""
+metadata metablock(s): test infrastructure, independent of the C++ reader (plan_parts in
+brotli-lib_amd/csrc/decode_plan.h, which tests/test_decode_plan_host.py holds against this one)."""
 import numpy as np
 
 MAGIC = 0x3170424D

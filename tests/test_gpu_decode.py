@@ -74,6 +74,39 @@ def test_batch_decode_matches_oracle():
     assert outs == exps
 
 
+def test_mixed_batch_with_and_without_a_dictionary_handle():
+    """One list through decode_batch(...) and decode_batch(..., dictionary=d), d a small dictionary
+    no stream refers to: an empty input, a one-metablock stream, a two-metablock stream of 1 MiB of
+    zeros (25 bytes: its slot is 8x that, so it outgrows it and is decoded again alone), the same
+    cut 10 bytes short, and a part-indexed stream.  Same bytes and the same error from both; the
+    indexed stream decodes on one wave in the plain call's launch and part-parallel, alone, with
+    the handle."""
+    import _streams
+    half = 1 << 19
+    zeros = _streams.build(_streams.Stream(22, [_streams.MB('cmds', cmds=[(b'\0', half - 1, ('dist', 1))]) for _ in range(2)],
+                                           'zeros_1mib')).data
+    one = _streams.build(_streams.long_run(700, lgwin=16)).data
+    with open(os.path.join(G, 'parts', 'parts_enwik300k.br'), 'rb') as f:
+        indexed = f.read()
+    streams = [b'', one, zeros, zeros[:-10], indexed]
+    exps = [_oracle.decode(s) for s in streams]
+    assert isinstance(exps[0], int) and exps[1] == b'r' * 700 and exps[2] == bytes(2 * half) and isinstance(exps[3], int)
+    assert len(exps[4]) == 300000 and len(zeros) * 8 < 1 << 16
+
+    def check(outs):
+        got = [o.code if isinstance(o, brotli_amd.BrotliError) else o for o in outs]
+        print([g if isinstance(g, int) else len(g) for g in got])
+        assert got == exps
+
+    before = brotli_amd.part_stats()
+    check(brotli_amd.decode_batch(streams))
+    assert brotli_amd.part_stats() == before
+    with brotli_amd.Dictionary(bytes(range(256)) * 4) as d:
+        check(brotli_amd.decode_batch(streams, dictionary=d))
+    after = brotli_amd.part_stats()
+    assert (after[0] - before[0], after[1] - before[1]) == (1, 0)
+
+
 def test_decode_options_semantics():
     """maxOutputSize (decode.ts:46-62), legacy outputSize truncation / zero padding (engine.ts:2210-2220)"""
     with open(os.path.join(G, 'vectors', 'alice29.txt.compressed'), 'rb') as f:

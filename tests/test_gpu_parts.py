@@ -134,7 +134,7 @@ class _W:   # LSB-first bit writer
 
 def test_index_pointing_into_its_own_payload_is_not_followed():
     """An index whose first entry is not the metablock right after the index block is not
-    trusted (runtime.cpp plan_parts).  Here the metadata payload hides a second, complete
+    trusted (decode_plan.h plan_parts).  Here the metadata payload hides a second, complete
     metablock sequence (stream B) and the entries point into it; every part of B would check
     out against entries describing B.  The reference decoder skips the payload and decodes
     what follows it (stream A): so must the GPU."""
