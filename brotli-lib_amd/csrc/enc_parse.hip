@@ -3,6 +3,7 @@
 #include <hipcub/hipcub.hpp>
 #include <cstdlib>
 
+#include "backtrack_window.h"
 #include "enc_common.h"
 
 namespace mib {
@@ -899,16 +900,56 @@ __global__ __launch_bounds__(64 * kDpWaves, KS == 8 ? 3 : KS == 4 ? MIB_DP_OCC_K
 // ---------------------------------------------------------------- 4. backtrack, wave per segment
 // computeShortestPathFromNodes / createCommandsFromPath (backward-references-hq.ts:384-406,
 // 610-673) without the distance ring: that is stitched per segment in enc_entropy.hip.
-// The path is walked from the segment end in windows of 64 positions: a ballot of the
-// window's copy nodes, then a scalar walk that skips each literal run with a bit scan and each
-// copy with its length.  The windows are aligned to the segment end and loaded four at a time
-// (a chunk of 256 positions), the next chunk in flight while this one is walked; the commands
-// gather in lanes (lane k: the k-th of a batch) and are stored 64 at a time.  (A load per
-// window issued when the walk reached it, and a store per command from lane 0, left the wave
-// waiting on every window: C4 backtrack 2.7 ms a launch.)
+// The path is walked from the segment end in windows of 64 positions, lane x holding the node
+// at offset x from the window's top.  The windows are aligned to the segment end and loaded
+// four at a time (a chunk of 256 positions), the next chunk in flight while this one is walked.
+// (A load per window issued when the walk reached it left the wave waiting on every window:
+// C4 backtrack 2.7 ms a launch.)
+//
+// A window with at least vec_min copy nodes is walked by the whole wave at once
+// (backtrack_window.h: the path by pointer doubling with ds_bpermute, lane k its k-th node):
+// the ballot of the path's copy nodes lists the window's commands in walk order, each copy
+// node's lane knows its command's rank and the literals that follow it, and stores its
+// command itself.  A window with fewer is walked on the scalar side, a copy node at a time (a
+// bit scan over the window's ballot, two v_readlane), lane 0 storing each command: that walk
+// is a dependent chain of some 35 scalar instructions a command on the one scalar unit the
+// CU's waves share, which at text's six commands a window kept the whole kernel waiting for
+// that unit; for a window of random bytes or inside a long literal run
+// it is the cheaper of the two.
+//
+// The walk's command q goes to out[cap - 1 - q]: the commands end up right-aligned in the
+// slice, in stream order.  A call that parses pieces (in_place) leaves them there and moves the
+// piece's cmd_off to them, where merge_pieces_kernel reads them; otherwise they move to the
+// slice's front.
+//
+// Nothing zeroes `choice` between calls, and none of what an earlier call or pass left there
+// is read: dp_kernel stores the choice of every node it fetches (a batch's at the batch's
+// end, at the segment's end or before it jumps), and the only positions of a parsed range it
+// does not fetch are the interiors of the copies it takes outright (longer than kLongCopy).
+// The walk reaches such a copy's end node, which was fetched after the jump, and leaves it by
+// the copy's length for the node the jump was taken from, which was stored before it; every
+// other node of the path is the predecessor, by a literal or a relaxed copy, of a fetched
+// node inside the range.  Node a belongs to the previous segment and is excluded by the
+// load's p > a.  A stale lane of a window's ballot, or of next[], matters only if the path
+// reaches it, which it does not; and whatever the choices hold, a length beyond the
+// segment's start counts as a literal and a command beyond the slice is not stored.
 constexpr int kBtWin = 4;   // windows per chunk
+// vec_min for the product (the experiments build: MIB_BT_VEC_MIN; 65: the scalar walk alone)
+constexpr int kBtVecMin = 2;
+struct BtDevWave {   // the wave as backtrack_window.h's lanes
+  typedef uint32_t Reg;
+  uint32_t lane;
+  static __device__ __forceinline__ uint32_t at(const Reg &r, uint32_t) { return r; }
+  template <class F>
+  __device__ __forceinline__ Reg each(F f) const { return f(lane); }
+  __device__ __forceinline__ Reg gather(const Reg &idx, const Reg &v) const { return bperm(idx, v); }
+  __device__ __forceinline__ uint64_t ballot(const Reg &r) const { return __ballot(r != 0); }
+  __device__ __forceinline__ uint32_t read(const Reg &r, uint32_t x) const {
+    return (uint32_t)__builtin_amdgcn_readlane((int)r, (int)x);
+  }
+};
 __global__ __launch_bounds__(64) void backtrack_kernel(const Job *jobs, Seg *segs, int nsegs, const uint64_t *choice,
-                                                       RawCmd *raw) {
+                                                       RawCmd *raw, int in_place, int vec_min) {
   const int s = blockIdx.x;
   const int lane = threadIdx.x;
   Seg &sg = segs[s];
@@ -917,26 +958,20 @@ __global__ __launch_bounds__(64) void backtrack_kernel(const Job *jobs, Seg *seg
   RawCmd *out = raw + sg.cmd_off;
   const uint32_t a = sg.start;
   const uint32_t cap = (sg.end - a) / 2 + 2;
-  uint32_t w = cap;   // commands are written from the end of the slice downward
+  uint32_t n = 0;   // commands so far
   uint32_t cur = sg.end, lits = 0, tail = 0;
   bool seen_copy = false;
   uint32_t pend_len = 0, pend_dist = 0, last_dist = 0;
-  // the batch of commands in lanes: lane k holds the k-th, stored at w - 1 - k
-  uint32_t bi = 0, bl = 0, bd = 0;
-  int nb = 0;
-  auto put = [&](uint32_t ins, uint32_t len, uint32_t dist) {
-    bi = lane == nb ? ins : bi;
-    bl = lane == nb ? len : bl;
-    bd = lane == nb ? dist : bd;
-    if (++nb == 64) {
-      RawCmd &o = out[w - 1 - lane];
-      o.ins = bi;
-      o.len = bl;
-      o.dist = bd;
-      w -= 64;
-      nb = 0;
+  auto put = [&](uint32_t ins, uint32_t len, uint32_t dist) {   // wave-uniform values
+    if (lane == 0 && n < cap) {
+      RawCmd &o = out[cap - 1 - n];
+      o.ins = ins;
+      o.len = len;
+      o.dist = dist;
     }
+    n++;
   };
+  const BtDevWave wv{(uint32_t)lane};
   auto load_chunk = [&](uint32_t top, uint64_t (&v)[kBtWin]) {   // windows top, top - 64, ...
 #pragma unroll
     for (int j = 0; j < kBtWin; j++) {
@@ -961,7 +996,39 @@ __global__ __launch_bounds__(64) void backtrack_kernel(const Job *jobs, Seg *seg
         if ((uint32_t)lane >= nvalid || len > p - a) len = 0;   // a literal is always a valid edge
         const uint32_t dist = (uint32_t)(v >> 32);
         const uint64_t copies = __ballot(len != 0);
-        uint32_t x = wtop - cur;
+        uint32_t x = wtop - cur;   // < nvalid
+        if (__popcll(copies) >= vec_min) {
+          uint32_t node, nlen;
+          const BtWindow r = bt_window(wv, len, x, nvalid, node, nlen);
+          const uint32_t nd = bperm(node, dist);
+          if (r.copies) {
+            const uint32_t k1 = bt_first(r.copies), kl = bt_last(r.copies);
+            // the literals up to the first copy node close the pending command
+            if (!seen_copy) {
+              tail = lits + k1;
+              seen_copy = true;
+              last_dist = wv.read(nd, k1);
+            } else {
+              put(lits + k1, pend_len, pend_dist);
+            }
+            // every copy node but the last: its command is complete
+            const uint32_t q = n + bt_rank(r.copies, (uint32_t)lane);
+            if (nlen != 0 && (uint32_t)lane != kl && q < cap) {
+              RawCmd &o = out[cap - 1 - q];
+              o.ins = bt_lits_after(r.copies, r.npath, (uint32_t)lane);
+              o.len = nlen;
+              o.dist = nd;
+            }
+            n += (uint32_t)__popcll(r.copies) - 1;
+            pend_len = wv.read(nlen, kl);
+            pend_dist = wv.read(nd, kl);
+            lits = bt_lits_after(r.copies, r.npath, kl);
+          } else {
+            lits += r.npath;
+          }
+          cur = wtop - r.exit;
+          continue;
+        }
         for (;;) {
           const uint64_t rest = x < 64 ? (copies >> x) : 0ull;
           const uint32_t y = rest ? x + (uint32_t)(__ffsll((unsigned long long)rest) - 1) : nvalid;
@@ -1004,28 +1071,23 @@ __global__ __launch_bounds__(64) void backtrack_kernel(const Job *jobs, Seg *seg
   }
   if (seen_copy) put(lits, pend_len, pend_dist);
   else tail = lits;
-  if (nb) {   // the last, partial batch
-    if (lane < nb) {
-      RawCmd &o = out[w - 1 - lane];
-      o.ins = bi;
-      o.len = bl;
-      o.dist = bd;
+  n = min(n, cap);
+  const uint32_t w = cap - n;   // the first command's place
+  if (!in_place) {
+    wave_sync();
+    // move the commands to the front of the slice; a chunk is read into registers before it
+    // is written, and a later chunk's source lies above every earlier chunk's destination
+    for (uint32_t q0 = 0; q0 < n; q0 += 64) {
+      RawCmd t;
+      const uint32_t q = q0 + lane;
+      if (q < n) t = out[w + q];
+      wave_sync();
+      if (q < n) out[q] = t;
+      wave_sync();
     }
-    w -= nb;
-  }
-  const uint32_t n = cap - w;
-  wave_sync();
-  // move the commands to the front of the slice; a chunk is read into registers before it
-  // is written, and a later chunk's source lies above every earlier chunk's destination
-  for (uint32_t q0 = 0; q0 < n; q0 += 64) {
-    RawCmd t;
-    const uint32_t q = q0 + lane;
-    if (q < n) t = out[w + q];
-    wave_sync();
-    if (q < n) out[q] = t;
-    wave_sync();
   }
   if (lane == 0) {
+    if (in_place) sg.cmd_off += w;
     sg.ncmd = n;
     sg.tail_lits = tail;
     sg.last_dist = last_dist;
@@ -1051,7 +1113,10 @@ __global__ __launch_bounds__(64) void merge_pieces_kernel(const Job *jobs, Seg *
   uint32_t n = 0, carry = 0, last = 0;
   for (int k = 0; k < P; k++) {
     const Seg &pc = mine[k];
-    const RawCmd *src = raw + pc.cmd_off;   // (at or above dst + n: chunks are read before they are written)
+    // the piece's commands where its backtrack left them, right-aligned in the piece's slice
+    // (at or above dst + n, and a later piece's above this one's slice: chunks are read before
+    // they are written)
+    const RawCmd *src = raw + pc.cmd_off;
     uint32_t m = pc.ncmd;
     if (m && n && carry == 0) {   // the previous piece ended in a copy: does this one continue it?
       const RawCmd f = src[0], p = dst[n - 1];
@@ -1545,8 +1610,10 @@ void launch_cost_model(hipStream_t st, const Job *jobs, int njobs, const Seg *se
   hipLaunchKernelGGL(cmd_stats_kernel, dim3(nsegs), dim3(256), 0, st, jobs, segs, raw, hist);
   hipLaunchKernelGGL(cost_model_kernel, dim3(njobs), dim3(256), 0, st, hist, model);
 }
-void launch_backtrack(hipStream_t st, const Job *jobs, Seg *segs, int nsegs, const uint64_t *choice, RawCmd *raw) {
-  hipLaunchKernelGGL(backtrack_kernel, dim3(nsegs), dim3(64), 0, st, jobs, segs, nsegs, choice, raw);
+// in_place: segs are a call's parse pieces, which merge_pieces_kernel joins
+void launch_backtrack(hipStream_t st, const Job *jobs, Seg *segs, int nsegs, const uint64_t *choice, RawCmd *raw, bool in_place) {
+  static const int vec_min = knob("MIB_BT_VEC_MIN") ? atoi(knob("MIB_BT_VEC_MIN")) : kBtVecMin;   // experiments
+  hipLaunchKernelGGL(backtrack_kernel, dim3(nsegs), dim3(64), 0, st, jobs, segs, nsegs, choice, raw, in_place ? 1 : 0, vec_min);
 }
 
 }  // namespace enc

@@ -584,7 +584,7 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
     // lit_h, hl, hc, hd lie back to back in the arena (taken in that order): one memset
     CK(hipMemsetAsync(lit_h, 0, reinterpret_cast<uint8_t *>(hd + nm1 * kMaxBT * kDistCtx * 128) -
                                     reinterpret_cast<uint8_t *>(lit_h), st));
-    CK(hipMemsetAsync(choice, 0, ((size_t)total + 1) * 8, st));
+    // (choice is not zeroed: the backtrack reads only what this call's parse stored, enc_parse.hip)
     const int depth = (int)env_u32("MIB_DEPTH", (uint32_t)depth_for_quality(prm.quality), 1, 64);   // override: experiments
     // (a batch of many metablocks fills the chip with each launch: there the independent
     // launches ran side by side were slower, C4 encode -1.8 %, r05ap)
@@ -649,7 +649,7 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
               s1 == d_fin && ps ? min_pshift : 0);
     tm.stop();
     tm.start("backtrack");
-    launch_backtrack(st, d_jobs, s1, n1, choice, raw);
+    launch_backtrack(st, d_jobs, s1, n1, choice, raw, ps && s1 == d_fin);
     tm.stop();
     if (two_pass) {   // iteration 2: prices from the first parse's commands
       tm.start("cost_model");
@@ -660,7 +660,7 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
                 ps ? min_pshift : 0);
       tm.stop();
       tm.start("backtrack");
-      launch_backtrack(st, d_jobs, d_fin, nfin, choice, raw);
+      launch_backtrack(st, d_jobs, d_fin, nfin, choice, raw, ps);
       tm.stop();
     }
     if (ps) launch_merge_pieces(st, d_jobs, d_segs, nsegs, d_pieces, raw);
