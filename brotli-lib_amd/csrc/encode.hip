@@ -362,6 +362,68 @@ const DictDev *dict_device(int dev) {
   return &d;
 }
 
+// The match search of a call, one piece of code for encode_group and the diagnostic entry
+// mib_debug_match_passes: which streams are searched and with what (match_job), and the order
+// of the launches (launch_match_search).
+// a stream written uncompressed: no match search
+bool stored_stream(const Params &prm, uint64_t n) { return prm.quality == 0 || n < 64; }
+// static-dictionary words: one-shot streams at q10+ whose window distances stay below the
+// words' flag (kDictFlag), beside a custom dictionary of less than 4 MiB (below)
+bool dict_words(const Params &prm, const StreamDesc &sd, bool stored) {
+  return !stored && sd.cdict_len < (1u << 22) && !sd.streaming && !sd.hist_tab && prm.quality >= 10 && prm.lgwin <= 22 &&
+         dict_enabled();
+}
+struct MatchSearch {   // what the call's streams need, gathered by match_job
+  bool any_hist = false, any_parts = false, any_dict = false, any_cdict = false, cdict_std = false;
+  const uint32_t *cdict_tab = nullptr;
+};
+// the Job fields the match search reads, from the stream's description
+void match_job(Job &jb, const Params &prm, const StreamDesc &sd, MatchSearch &ms) {
+  jb.data = sd.d_data;
+  jb.n = (uint32_t)sd.n;
+  jb.lgwin = (uint32_t)prm.lgwin;
+  jb.uncompressed = stored_stream(prm, sd.n) ? 1 : 0;
+  jb.font = prm.font ? 1 : 0;
+  jb.hist = sd.hist;
+  jb.abs_base = sd.abs_base;
+  jb.win_abs = sd.win_abs;
+  jb.hist_tab = sd.hist_tab;
+  // (the kHist builds: a chunk with bytes before data[0]; every BrotliEncoder chunk has the table)
+  if (jb.hist_tab || jb.hist) ms.any_hist = true;
+  // custom dictionary: its tail copies (kCDictMark records) beside the static words, whose
+  // distances it shifts by its length (the decoder addresses it first, engine.ts:907-913);
+  // a word's flagged distance must stay below 2^23, so words need a dictionary < 4 MiB
+  if (!jb.uncompressed && sd.cdict) {
+    jb.cdict = sd.cdict;
+    jb.cdict_len = sd.cdict_len;
+    jb.cdict_tail4 = sd.cdict_tail4;
+    ms.any_cdict = true;
+    // (one dictionary a call: every stream that has one has the same)
+    if (sd.cdict_std) ms.cdict_std = true, ms.cdict_tab = sd.cdict_tab, jb.cdict_std = 1;
+  }
+  jb.dict = dict_words(prm, sd, jb.uncompressed != 0) ? 1 : 0;
+  jb.dict_span = dict_span();
+  if (jb.dict) ms.any_dict = true;
+}
+// The passes after the candidate walk (the bits of mib_debug_match_passes' `passes`, and the
+// prepared dictionary's lookup, which that entry leaves out); encode_group runs them all.
+constexpr int kPassNear = 1, kPassWords = 2, kPassTail = 4, kPassLookup = 8, kPassAll = 15;
+// The launches, in their order: the walk, then into the records it left empty the static words
+// (dd: dict_device(), for a call with any_dict) and the custom dictionary's tail copies, then the
+// near scan, which merges into records that hold no dictionary copy, then the prepared
+// dictionary's lookup.  Each pass of `passes` runs where the call's options and streams have it.
+void launch_match_search(hipStream_t st, const Params &prm, const MatchSearch &ms, int passes, const DictDev *dd, const Job *d_jobs,
+                         int k, const uint32_t *d_seg_job, const SegRef *d_seg_ref, const uint32_t *skeys, const uint32_t *svals,
+                         uint32_t total, uint32_t *matches) {
+  const int depth = (int)env_u32("MIB_DEPTH", (uint32_t)depth_for_quality(prm.quality), 1, 64);   // override: experiments
+  const uint32_t max_dist = (1u << prm.lgwin) - 16;
+  launch_find_matches(st, d_jobs, d_seg_job, d_seg_ref, skeys, svals, total, depth, max_dist, ms.any_hist, ms.any_parts, matches);
+  if ((passes & kPassWords) && dd) launch_dict_matches(st, d_jobs, k, dict_span(), dd->tab, dd->data, matches);
+  if ((passes & kPassTail) && ms.any_cdict && !ms.cdict_std) launch_cdict_matches(st, d_jobs, d_seg_job, total, matches);
+  if ((passes & kPassNear) && near_scan(prm)) launch_near_matches(st, d_jobs, d_seg_job, d_seg_ref, total, max_dist, ms.any_hist, ms.any_parts, matches);
+  if ((passes & kPassLookup) && ms.cdict_tab) launch_cdict_lookup(st, d_jobs, d_seg_job, total, ms.cdict_tab, hash_bytes(prm), matches);
+}
+
 // Encode a group of streams into d_out (packed from out_pos; returns the per-stream sizes).
 int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k, uint8_t *d_out, uint64_t out_cap,
                  uint64_t out_pos, uint64_t *sizes, int32_t (*dc_out)[4], hipStream_t st, void **ws_slot) {
@@ -375,47 +437,22 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
   // of earlier segments' 2^shift, so a multiple of 2^min_pshift, and its pieces follow it -- any
   // 2^min_pshift (or fewer, a power of two) pieces aligned at their count lie in one segment
   int min_pshift = kMaxPieceShift;
-  bool any_hist = false, any_parts = false, any_dict = false, any_cdict = false, cdict_std = false;
-  const uint32_t *cdict_tab = nullptr;
+  MatchSearch ms;
   for (size_t j = 0; j < k; j++) {
     Job &jb = jobs[j];
     memset(&jb, 0, sizeof(jb));
     const uint64_t n = sd[j].n;
-    jb.data = sd[j].d_data;
-    jb.n = (uint32_t)n;
-    jb.lgwin = (uint32_t)prm.lgwin;
+    match_job(jb, prm, sd[j], ms);
     jb.npostfix = (uint32_t)prm.npostfix;
     jb.ndirect = (uint32_t)prm.ndirect;
-    jb.uncompressed = (prm.quality == 0 || n < 64) ? 1 : 0;
-    jb.font = prm.font ? 1 : 0;
     jb.hq = prm.quality >= 10 ? 1 : 0;
     jb.hdr_lgwin = sd[j].hdr_lgwin;
     jb.final_ = sd[j].final_;
     for (int q = 0; q < 4; q++) jb.dc_in[q] = jb.dc_out[q] = sd[j].dc[q];
     jb.prev_bytes = sd[j].prev_bytes;
-    jb.hist = sd[j].hist;
-    jb.abs_base = sd[j].abs_base;
-    jb.win_abs = sd[j].win_abs;
-    jb.hist_tab = sd[j].hist_tab;
-    if (jb.hist_tab) any_hist = true;
     jb.out_base = sd[j].out_base;
     jb.parts = (!jb.uncompressed && wants_parts(sd[j])) ? 1 : 0;
-    // custom dictionary: its tail copies (kCDictMark records) beside the static words, whose
-    // distances it shifts by its length (the decoder addresses it first, engine.ts:907-913);
-    // a word's flagged distance must stay below 2^23, so words need a dictionary < 4 MiB
-    if (!jb.uncompressed && sd[j].cdict) {
-      jb.cdict = sd[j].cdict;
-      jb.cdict_len = sd[j].cdict_len;
-      jb.cdict_tail4 = sd[j].cdict_tail4;
-      any_cdict = true;
-      // (one dictionary a call: every stream that has one has the same)
-      if (sd[j].cdict_std) cdict_std = true, cdict_tab = sd[j].cdict_tab, jb.cdict_std = 1;
-    }
-    jb.dict = (!jb.uncompressed && jb.cdict_len < (1u << 22) && !sd[j].streaming && !sd[j].hist_tab && prm.quality >= 10 && prm.lgwin <= 22 &&
-               dict_enabled()) ? 1 : 0;
-    jb.dict_span = dict_span();
-    if (jb.dict) any_dict = true;
-    if (jb.parts) any_parts = true;
+    if (jb.parts) ms.any_parts = true;
     uint64_t idx_extra = 0;
     if (jb.parts) {
       jb.part_bits = part_bits();
@@ -585,11 +622,10 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
     CK(hipMemsetAsync(lit_h, 0, reinterpret_cast<uint8_t *>(hd + nm1 * kMaxBT * kDistCtx * 128) -
                                     reinterpret_cast<uint8_t *>(lit_h), st));
     // (choice is not zeroed: the backtrack reads only what this call's parse stored, enc_parse.hip)
-    const int depth = (int)env_u32("MIB_DEPTH", (uint32_t)depth_for_quality(prm.quality), 1, 64);   // override: experiments
     // (a batch of many metablocks fills the chip with each launch: there the independent
     // launches ran side by side were slower, C4 encode -1.8 %, r05ap)
-    const DictDev *dd = any_dict ? dict_device(mib_ctx_device_of(ctx)) : nullptr;
-    if (any_dict && !dd) return MIB_E_OUT_OF_MEMORY;   // (before the fork: nothing queued on the side stream yet)
+    const DictDev *dd = ms.any_dict ? dict_device(mib_ctx_device_of(ctx)) : nullptr;
+    if (ms.any_dict && !dd) return MIB_E_OUT_OF_MEMORY;   // (before the fork: nothing queued on the side stream yet)
     Fork fk = nmbs * 3 <= 256 ? fork_of(ws, st) : Fork{st, st, nullptr, nullptr};
     // every exit from here on (a failed launch check included) leaves st ordered after the side
     // stream's work, so the next call's memsets on st cannot overtake its kernels
@@ -609,14 +645,9 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
     launch_sort(st, d_jobs, d_seg_job, (int)k, total, hash_bytes(prm), sort_ws, keys, vals, skeys, svals);
     tm.stop();
     tm.start("find_matches");
-    launch_find_matches(st, d_jobs, d_seg_job, d_seg_ref, skeys, svals, total, depth, (1u << prm.lgwin) - 16, any_hist,
-                        any_parts, matches);
-    if (dd) launch_dict_matches(st, d_jobs, (int)k, dict_span(), dd->tab, dd->data, matches);
-    if (any_cdict && !cdict_std) launch_cdict_matches(st, d_jobs, d_seg_job, total, matches);
-    if (near_scan(prm)) launch_near_matches(st, d_jobs, d_seg_job, d_seg_ref, total, (1u << prm.lgwin) - 16, any_hist, any_parts, matches);
-    if (cdict_tab) launch_cdict_lookup(st, d_jobs, d_seg_job, total, cdict_tab, hash_bytes(prm), matches);
+    launch_match_search(st, prm, ms, kPassAll, dd, d_jobs, (int)k, d_seg_job, d_seg_ref, skeys, svals, total, matches);
     if (!forked) {
-      if (any_hist) launch_hist_update(st, d_jobs, d_seg_job, skeys, svals, total);
+      if (ms.any_hist) launch_hist_update(st, d_jobs, d_seg_job, skeys, svals, total);
       launch_lit_histo(st, d_jobs, d_segs, nsegs, lit_h);
     }
     // (the parse's candidates go by the metablocks' context modes)
@@ -641,11 +672,11 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
     }
     // the history table's update (read by the next call's match search): beside the parse
     fk.fork();
-    if (forked && any_hist) launch_hist_update(fk.side, d_jobs, d_seg_job, skeys, svals, total);
+    if (forked && ms.any_hist) launch_hist_update(fk.side, d_jobs, d_seg_job, skeys, svals, total);
     tm.start(two_pass ? "dp_sample" : "dp_parse");
     Seg *s1 = sampled ? d_sample : two_pass ? d_segs : d_fin;
     const int n1 = s1 == d_fin ? nfin : nsegs;
-    launch_dp(st, d_jobs, s1, n1, lit_h, nullptr, matches, choice, any_cdict, prm.font, pos_words, ring_hist, d_mbs,
+    launch_dp(st, d_jobs, s1, n1, lit_h, nullptr, matches, choice, ms.any_cdict, prm.font, pos_words, ring_hist, d_mbs,
               s1 == d_fin && ps ? min_pshift : 0);
     tm.stop();
     tm.start("backtrack");
@@ -656,7 +687,7 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
       launch_cost_model(st, d_jobs, (int)k, s1, nsegs, raw, model_h, model);
       tm.stop();
       tm.start("dp_parse");
-      launch_dp(st, d_jobs, d_fin, nfin, lit_h, model, matches, choice, any_cdict, prm.font, pos_words, ring_hist, d_mbs,
+      launch_dp(st, d_jobs, d_fin, nfin, lit_h, model, matches, choice, ms.any_cdict, prm.font, pos_words, ring_hist, d_mbs,
                 ps ? min_pshift : 0);
       tm.stop();
       tm.start("backtrack");
@@ -1288,16 +1319,19 @@ int mib_encode_batch_dictionary(const mib_span *in, size_t k, const mib_enc_opts
   return encode_host(in, k, o, d, out, status);
 }
 
-// Diagnostic (tests): the candidate walk alone.  The batch is laid out as encode_group lays a
-// call out (every stream on its own 64 KiB-aligned range of global positions, a spare segment
-// behind it), then only the bucket sort and find_matches run -- no history table, part index,
-// near scan or dictionary pass -- and each stream's records come back stream-relative.
-int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out) {
-  if (!k || !in || !out) return MIB_E_INVALID_ARG;
+// Diagnostic (tests): the match search pass by pass.  The batch is laid out as encode_group lays
+// a call out (every stream on its own 64 KiB-aligned range of global positions, a spare segment
+// behind it), the streams are described as the product describes them (fill_desc, match_job:
+// `history` bytes of every buffer lie before its stream, as a BrotliEncoder chunk's window does,
+// without the history table), then the bucket sort and launch_match_search run with the passes
+// asked for -- no part index, no prepared dictionary -- and each stream's records come back
+// stream-relative.
+int mib_debug_match_passes(const mib_span *in, size_t k, const mib_enc_opts *o, int passes, uint32_t history, mib_buf *out) {
+  if (!k || !in || !out || (passes & ~(kPassNear | kPassWords | kPassTail))) return MIB_E_INVALID_ARG;
   for (size_t i = 0; i < k; i++) {
     out[i].data = nullptr;
     out[i].size = 0;
-    if ((!in[i].data && in[i].size) || in[i].size >= (1ull << 31)) return MIB_E_INVALID_ARG;
+    if ((!in[i].data && in[i].size) || in[i].size >= (1ull << 31) || in[i].size < history) return MIB_E_INVALID_ARG;
   }
   DefaultLock use;
   mib_ctx *c = mib_default_ctx();
@@ -1311,7 +1345,7 @@ int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o,
   std::vector<uint32_t> seg_job;
   std::vector<SegRef> seg_ref;
   uint64_t pos_total = 0;
-  for (size_t j = 0; j < k; j++) pos_total += ((in[j].size + kSeg - 1) / kSeg) * kSeg + kSeg;
+  for (size_t j = 0; j < k; j++) pos_total += ((in[j].size - history + kSeg - 1) / kSeg) * kSeg + kSeg;
   if (pos_total >= (1ull << 31)) return MIB_E_INVALID_ARG;
   const uint32_t total = (uint32_t)pos_total;
   const size_t sort_tmp = sort_ws_bytes(total);
@@ -1321,8 +1355,16 @@ int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o,
   if (hipMalloc(&buf, need) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
   struct FreeAtExit {
     uint8_t *p;
-    ~FreeAtExit() { hipFree(p); }
-  } free_at_exit{buf};
+    DevDict dict;
+    ~FreeAtExit() {
+      dict.release();
+      hipFree(p);
+    }
+  } own{buf, {}};
+  if (o) {
+    const int rc = own.dict.upload(o->dict, o->dict_len, st);
+    if (rc) return rc;
+  }
   Arena ar{buf};
   uint8_t *d_in = ar.take<uint8_t>(ioff[k] + 64);
   uint32_t *keys = ar.take<uint32_t>(total), *vals = ar.take<uint32_t>(total);
@@ -1333,16 +1375,17 @@ int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o,
   uint32_t *d_seg_job = ar.take<uint32_t>(total >> kSegBits);
   SegRef *d_seg_ref = ar.take<SegRef>(total >> kSegBits);
   if (ar.off > need) return MIB_E_OUT_OF_MEMORY;
+  MatchSearch ms;
   pos_total = 0;
   for (size_t j = 0; j < k; j++) {
     Job &jb = jobs[j];
     memset(&jb, 0, sizeof(jb));
-    const uint64_t n = in[j].size;
-    jb.data = d_in + ioff[j];
-    jb.n = (uint32_t)n;
-    jb.lgwin = (uint32_t)prm.lgwin;
-    jb.uncompressed = (prm.quality == 0 || n < 64) ? 1 : 0;
-    jb.font = prm.font ? 1 : 0;
+    const uint64_t n = in[j].size - history;
+    StreamDesc sd;
+    fill_desc(sd, d_in + ioff[j] + history, n, prm, history == 0);
+    sd.hist = sd.abs_base = sd.win_abs = history;
+    if (own.dict.d) own.dict.attach(sd);
+    match_job(jb, prm, sd, ms);
     jb.pos_base = (uint32_t)pos_total;
     const uint64_t span = ((n + kSeg - 1) / kSeg) * kSeg + kSeg;
     for (uint64_t q = 0; q < span / kSeg; q++) {
@@ -1351,6 +1394,8 @@ int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o,
     }
     pos_total += span;
   }
+  const DictDev *dd = (passes & kPassWords) && ms.any_dict ? dict_device(mib_ctx_device_of(c)) : nullptr;
+  if ((passes & kPassWords) && ms.any_dict && !dd) return MIB_E_OUT_OF_MEMORY;
   CK(hipMemsetAsync(d_in, 0, ioff[k] + 64, st));
   for (size_t j = 0; j < k; j++)
     if (in[j].size) CK(hipMemcpyAsync(d_in + ioff[j], in[j].data, in[j].size, hipMemcpyHostToDevice, st));
@@ -1358,9 +1403,8 @@ int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o,
   CK(hipMemcpyAsync(d_seg_job, seg_job.data(), seg_job.size() * 4, hipMemcpyHostToDevice, st));
   CK(hipMemcpyAsync(d_seg_ref, seg_ref.data(), seg_ref.size() * sizeof(SegRef), hipMemcpyHostToDevice, st));
   CK(hipMemsetAsync(matches, 0, (size_t)total * kMatchRec * 4, st));
-  const int depth = (int)env_u32("MIB_DEPTH", (uint32_t)depth_for_quality(prm.quality), 1, 64);
   launch_sort(st, d_jobs, d_seg_job, (int)k, total, hash_bytes(prm), sort_ws, keys, vals, skeys, svals);
-  launch_find_matches(st, d_jobs, d_seg_job, d_seg_ref, skeys, svals, total, depth, (1u << prm.lgwin) - 16, false, false, matches);
+  launch_match_search(st, prm, ms, passes, dd, d_jobs, (int)k, d_seg_job, d_seg_ref, skeys, svals, total, matches);
   CK(hipGetLastError());
   CK(hipStreamSynchronize(st));
   std::vector<mib_buf *> outs(k);
@@ -1369,9 +1413,13 @@ int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o,
   for (size_t j = 0; j < k; j++) {
     outs[j] = &out[j];
     src[j] = reinterpret_cast<const uint8_t *>(matches + (size_t)jobs[j].pos_base * kMatchRec);
-    lens[j] = (uint64_t)in[j].size * kMatchRec * 4;
+    lens[j] = (uint64_t)jobs[j].n * kMatchRec * 4;
   }
   return mib_bufs_from_device(k, outs.data(), src.data(), lens.data());
+}
+// the candidate walk alone: no pass after it, no history
+int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out) {
+  return mib_debug_match_passes(in, k, o, 0, 0, out);
 }
 
 // BrotliEncoder (encode.ts:290-409): input is taken in whole blocks of 2^lgblock

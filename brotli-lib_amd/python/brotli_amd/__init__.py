@@ -240,6 +240,9 @@ def _L():
         if hasattr(lib, 'mib_debug_match_records'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_debug_match_records.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts),
                                                     ctypes.POINTER(_Buf)]
+        if hasattr(lib, 'mib_debug_match_passes'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_debug_match_passes.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts), ctypes.c_int,
+                                                   ctypes.c_uint32, ctypes.POINTER(_Buf)]
         if hasattr(lib, 'mib_debug_prefix_codes'):   # (a BROTLI_AMD_LIB build may predate it)
             lib.mib_debug_prefix_codes.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(_Buf)]
         lib.mib_default_ctx.restype = ctypes.c_void_p
@@ -654,21 +657,28 @@ def debug_dp_launches():
     return {1: out[0], 2: out[1], 4: out[2], 8: out[3]}
 
 
-def debug_match_records(buffers, options=None):
-    """Diagnostic (tests): the records the encoder's bucket sort and candidate walk alone give
-    a batch of buffers (mib_debug_match_records): per buffer a numpy uint32 array of shape
-    (len(buffer), entries), each entry length << 24 | distance, valid ones first, 0 after."""
+def debug_match_records(buffers, options=None, passes=0, history=0):
+    """Diagnostic (tests): the records the encoder's match search gives a batch of buffers, pass
+    by pass (mib_debug_match_passes): the bucket sort and the candidate walk, then the passes of
+    the bit set `passes` where an encode call with these options runs them -- 1 the near scan, 2
+    static-dictionary words, 4 the tail copies of options['customDictionary'].  The first
+    `history` bytes of every buffer lie before its stream (a streaming chunk's window).  Per
+    buffer a numpy uint32 array of shape (len(buffer) - history, entries), each entry
+    length << 24 | distance, valid ones first, 0 after (include/brotli_amd.h has the formats)."""
     import numpy as np
     k = len(buffers)
     keep = [_in(b) for b in buffers]
     spans = (_Span * k)(*[_Span(_addr(a), n) for a, n, _ in keep])
     outs = (_Buf * k)()
-    rc = _L().mib_debug_match_records(spans, k, ctypes.byref(_opts(options)), outs)
+    if passes or history:
+        rc = _L().mib_debug_match_passes(spans, k, ctypes.byref(_opts(options)), int(passes), int(history), outs)
+    else:
+        rc = _L().mib_debug_match_records(spans, k, ctypes.byref(_opts(options)), outs)
     if rc:
         raise _err(rc)
     res = []
     for i in range(k):
-        n = keep[i][1]
+        n = keep[i][1] - history
         a = np.frombuffer(_take(outs[i]), dtype='<u4')
         res.append(a.reshape(n, -1) if n else a.reshape(0, 4))
     return res

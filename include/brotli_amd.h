@@ -296,6 +296,30 @@ void mib_debug_dp_launches(uint64_t out[4]);
  * the product build) little-endian u32, each length << 24 | distance with stream-relative
  * positions, valid entries first, longest last, zeros after. */
 int mib_debug_match_records(const mib_span *in, size_t k, const mib_enc_opts *o, mib_buf *out);
+/* Diagnostic (tests): the match search pass by pass, as an encode call with the options `o`
+ * runs it.  mib_debug_match_records is this entry with passes = 0 and history = 0.  After the
+ * bucket sort and the candidate walk the passes of the bit set `passes` run, in the encoder's
+ * order and each only where the encoder runs it for these options and streams (the encoder's
+ * own conditions and launch sequence, shared code):
+ *   2  static-dictionary words (one-shot streams at quality >= 10 and lgwin <= 22, the first
+ *      64 KiB of a stream), through the encoder's device word table;
+ *   4  the custom dictionary's tail copies, the dictionary being o->dict / o->dict_len (streams
+ *      that are not stored; a dictionary of fewer than four bytes gives none);
+ *   1  the near scan (quality >= 10, not in FONT mode), last: it merges into the records.
+ * Any other bit is MIB_E_INVALID_ARG.  The prepared dictionary's lookup (mib_dictionary) and the
+ * part index are not run.  history: the first `history` bytes of every buffer lie before its
+ * stream, as the window lies before a BrotliEncoder chunk (there is no history table: the walk
+ * sees the stream's own positions, the near scan reaches back into the history bytes; a chunk
+ * gets no static words); every buffer must hold at least that many bytes.  out[i] receives the
+ * records of the size - history positions after the history, in mib_debug_match_records' layout.
+ * Beside the walk's entries (length << 24 | distance) a record can hold:
+ *   a near entry   length << 24 | d, 1 <= d <= 63, length 2 .. 32, in front of the walk's
+ *                  entries longer than the longest near entry (a full record drops from the front);
+ *   a word         length << 24 | 1 << 23 | index, the identity transform of word `index` of
+ *                  that length in the RFC 7932 dictionary: the record's only entry;
+ *   a custom tail  length << 24 | 0xFFFFFF, the last `length` bytes of the custom dictionary:
+ *                  the record's only entry. */
+int mib_debug_match_passes(const mib_span *in, size_t k, const mib_enc_opts *o, int passes, uint32_t history, mib_buf *out);
 /* Diagnostic (tests): the encoder's Huffman kernel alone on chosen histograms.  alphabet[i] is
  * 256 (a literal code), 704 (a command code) or 64 (a distance code, NPOSTFIX 0 and NDIRECT 0);
  * hist holds the k histograms back to back, histogram i as alphabet[i] u32 counts.  They are
