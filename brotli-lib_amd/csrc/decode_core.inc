@@ -2679,6 +2679,8 @@ __device__ __forceinline__ int decompress(DecS &s, int8_t *dist_extra, int32_t *
           // holds any metablock's rest), so the stream is invalid: it ends, without the
           // stores, in what the copy ends in -- past the dictionary's end the reference's
           // TypeError, else the metablock below zero (-10).
+          // (A prepared dictionary's copy, cd_std, never passes the dictionary's end --
+          // use_dictionary refused it with -9 -- so only the -10 arm can fire for it.)
           const int len = s.cd_br_length - s.cd_br_copied;
           if ((int64_t)s.pos + len > (int64_t)s.ring_cap) return len > s.cd_total - s.cd_br_offset ? MIB_E_JS_TYPE_ERROR : ERR(s, -10);
         }
@@ -2692,6 +2694,9 @@ __device__ __forceinline__ int decompress(DecS &s, int8_t *dist_extra, int32_t *
           // whole output chunk came back: a copy from a customDictionary that reaches the ring's
           // end ends the decoding there (the rest of a known size is zeros).  Kept for that
           // path, byte for byte; a prepared dictionary's copy goes on behind the flush.
+          // (Stream mode never gets here, under either rule: the fence is the ring size 2^30 or
+          // above, the copy ended at or below ring_cap -- the guard above -- and ring_cap < 2^30,
+          // stream_run's check and stream_session.h's static_assert.  The one-shot kernels do.)
           if (s.cd_std) continue;
           return 2;
         }

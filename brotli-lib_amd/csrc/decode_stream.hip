@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64) void decode_resume_kernel(StreamJob *jobs, int 
     dj.out_size = -1;
     dj.dict = job.dict;
     dj.dict_len = job.dict_len;
-    dj.dict_std = 0;   // (sessions keep the reference's rule)
+    dj.dict_std = job.dict_std;   // (a session made with a handle: the standard rule; else the reference's)
     DecS &s = *(DecS *)&g_dec;
     dec_init(s, dj, job.buf, tables, ctx, block_trees, tab, tab_cap);
     const int status = stream_run(s, job, &ctl, dist_extra, dist_offset, ctxmap_table);

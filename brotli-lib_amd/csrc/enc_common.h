@@ -108,6 +108,9 @@ struct Job {                // one stream (or streaming chunk) to encode
                             // text (the parse's distance-cache candidates run there)
   uint32_t cdict_std;       // 1: cdict is a prepared dictionary (mib_dictionary): copies from anywhere
                             // in it (cdict_lookup_kernel), no tail copies (is_cdict_push)
+  const uint32_t *cdict_tab; // ... and its index for the call's key length (kCDictWays), or null: the
+                            // dictionary is shorter than the key.  Per stream: the sessions of one
+                            // mib_encoder_update_batch may hold different dictionaries
 };
 
 // Per 64 KiB of global positions: where its stream's bytes are, so the match finder's gather
@@ -532,7 +535,7 @@ void launch_dict_matches(hipStream_t st, const Job *jobs, int njobs, uint32_t sp
                          const uint8_t *dict_data, uint32_t *matches);
 void launch_cdict_matches(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, uint32_t *matches);
 void launch_cdict_index(hipStream_t st, const uint8_t *dict, uint32_t n, int hb, uint32_t *tab);
-void launch_cdict_lookup(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, const uint32_t *tab, int hb,
+void launch_cdict_lookup(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, int hb,
                          uint32_t *matches);
 void launch_find_matches(hipStream_t st, const Job *jobs, const uint32_t *pos_job, const SegRef *seg_ref,
                          const uint32_t *skeys, const uint32_t *svals, uint32_t total, int depth, uint32_t max_dist,
@@ -569,7 +572,7 @@ void launch_split(hipStream_t st, hipStream_t side, const Job *jobs, Mb *mbs, in
                   const uint32_t *unit_h, Codes *codes, int max_units, int max_short_units);
 void launch_histo(hipStream_t st, const Job *jobs, const Seg *segs, const Mb *mbs, int nsegs, const Cmd *cmds,
                   const uint32_t *cmd_pos, const Unit *units, uint32_t *hl, uint32_t *hc, uint32_t *hd);
-void launch_dist_ring(hipStream_t st, Job *jobs, int njobs, const Seg *segs, const Cmd *cmds);
+void launch_dist_ring(hipStream_t st, Job *jobs, int njobs, const Seg *segs, const Cmd *cmds, const uint32_t *cmd_pos);
 void launch_context_mode(hipStream_t st, const Job *jobs, Mb *mbs, int nmbs);
 void launch_cluster(hipStream_t st, const Job *jobs, Mb *mbs, int nmbs, uint32_t *hl, uint32_t *hd);
 void launch_huffman(hipStream_t st, hipStream_t side, const Job *jobs, Mb *mbs, int nmbs, const uint32_t *hl,

@@ -698,8 +698,11 @@ __global__ __launch_bounds__(kCluT) void cluster_kernel(const Job *jobs, Mb *mbs
 
 // ---------------------------------------------------------------- distance ring after a chunk
 // (streaming: the next chunk's code-0 decisions start from it) lane per stream, backwards
-// over the last commands: every explicit distance was pushed.
-__global__ void dist_ring_kernel(Job *jobs, int njobs, const Seg *segs, const Cmd *cmds) {
+// over the last commands: every explicit distance was pushed, and so was a prepared
+// dictionary's copy whatever its code (is_cdict_push; cmd_pos: the position of each command's
+// insert, codes_kernel) -- a chunk that ends in a run of such copies at one distance hands on a
+// ring that holds the distance once per copy, as the decoder's does.
+__global__ void dist_ring_kernel(Job *jobs, int njobs, const Seg *segs, const Cmd *cmds, const uint32_t *cmd_pos) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= njobs) return;
   Job &jb = jobs[j];
@@ -709,8 +712,10 @@ __global__ void dist_ring_kernel(Job *jobs, int njobs, const Seg *segs, const Cm
   for (int s = (int)(jb.seg_base + jb.nseg) - 1; s >= (int)jb.seg_base && got < 4; s--) {
     const Seg &sg = segs[s];
     const Cmd *c = cmds + sg.cmd_off;
+    const uint32_t *cp = cmd_pos + sg.cmd_off;
     for (int q = (int)sg.ncmd - 1; q >= 0 && got < 4; q--)
-      if ((c[q].dist_prefix & 0x3FF) != 0 && !is_word(jb, c[q].dist)) ring[got++] = (int32_t)c[q].dist;
+      if (((c[q].dist_prefix & 0x3FF) != 0 && !is_word(jb, c[q].dist)) || is_cdict_push(jb, c[q].dist, cp[q] + c[q].ins))
+        ring[got++] = (int32_t)c[q].dist;
   }
   for (int q = 0; q < 4; q++) jb.dc_out[q] = q < got ? ring[q] : jb.dc_in[q - got];
 }
@@ -2683,8 +2688,8 @@ void launch_histo(hipStream_t st, const Job *jobs, const Seg *segs, const Mb *mb
   else
     hipLaunchKernelGGL(histo_kernel<256>, dim3(nsegs), dim3(256), 0, st, jobs, segs, mbs, cmds, cmd_pos, units, hl, hc, hd);
 }
-void launch_dist_ring(hipStream_t st, Job *jobs, int njobs, const Seg *segs, const Cmd *cmds) {
-  hipLaunchKernelGGL(dist_ring_kernel, dim3((njobs + 63) / 64), dim3(64), 0, st, jobs, njobs, segs, cmds);
+void launch_dist_ring(hipStream_t st, Job *jobs, int njobs, const Seg *segs, const Cmd *cmds, const uint32_t *cmd_pos) {
+  hipLaunchKernelGGL(dist_ring_kernel, dim3((njobs + 63) / 64), dim3(64), 0, st, jobs, njobs, segs, cmds, cmd_pos);
 }
 void launch_context_mode(hipStream_t st, const Job *jobs, Mb *mbs, int nmbs) {
   static const int force = knob("MIB_CTX_MODE") ? atoi(knob("MIB_CTX_MODE")) & 3 : -1;   // experiments

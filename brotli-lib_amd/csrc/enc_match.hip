@@ -639,7 +639,7 @@ __global__ __launch_bounds__(256) void cdict_matches_kernel(const Job *jobs, con
                                                             uint32_t *matches) {
   for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < total; g += gridDim.x * 256) {
     const Job &jb = jobs[pos_job[g >> kSegBits]];
-    if (!jb.cdict) continue;
+    if (!jb.cdict || jb.cdict_std) continue;   // (a prepared dictionary has no tail copies: cdict_lookup_kernel)
     const uint32_t q = g - jb.pos_base;
     if (q < 3 || q >= jb.n) continue;
     const uint8_t *d = jb.data;
@@ -688,12 +688,13 @@ __global__ __launch_bounds__(256) void cdict_index_kernel(const uint8_t *dict, u
 // bytes (the nearest of equals) is stored with its real distance at this position.  An address
 // whose distance the record cannot hold (sd::record_holds) ends the walk: the rest lie farther.
 __global__ __launch_bounds__(256) void cdict_lookup_kernel(const Job *jobs, const uint32_t *pos_job, uint32_t total,
-                                                           const uint32_t *tab, int hb, uint32_t *matches) {
+                                                           int hb, uint32_t *matches) {
   static_assert(sd::kMaxCopy == (uint32_t)kLongCopy, "shared_dict.h restates kLongCopy");
   static_assert(sd::kRecordDistLimit == kCDictMark && sd::kRecordWordFlag == kDictFlag, "shared_dict.h restates the record's format");
   for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < total; g += gridDim.x * 256) {
     const Job &jb = jobs[pos_job[g >> kSegBits]];
-    if (!jb.cdict) continue;   // (a stored stream)
+    const uint32_t *tab = jb.cdict_tab;   // the stream's own dictionary (null: none, a custom one, a stored stream)
+    if (!tab) continue;
     const uint32_t p = g - jb.pos_base;
     if (p >= jb.n || jb.n - p < (uint32_t)hb) continue;
     uint32_t *rec = matches + (uint64_t)g * kMatchRec;
@@ -722,10 +723,10 @@ void launch_cdict_index(hipStream_t st, const uint8_t *dict, uint32_t n, int hb,
   const unsigned grid = (unsigned)std::min<uint64_t>(16384, ((uint64_t)n + 255) / 256);
   hipLaunchKernelGGL(cdict_index_kernel, dim3(grid), dim3(256), 0, st, dict, n, hb, tab);
 }
-void launch_cdict_lookup(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, const uint32_t *tab, int hb,
+void launch_cdict_lookup(hipStream_t st, const Job *jobs, const uint32_t *pos_job, uint32_t total, int hb,
                          uint32_t *matches) {
   const unsigned grid = (unsigned)std::min<uint64_t>(16384, (total + 255) / 256);
-  hipLaunchKernelGGL(cdict_lookup_kernel, dim3(grid), dim3(256), 0, st, jobs, pos_job, total, tab, hb, matches);
+  hipLaunchKernelGGL(cdict_lookup_kernel, dim3(grid), dim3(256), 0, st, jobs, pos_job, total, hb, matches);
 }
 
 void launch_find_matches(hipStream_t st, const Job *jobs, const uint32_t *pos_job, const SegRef *seg_ref,

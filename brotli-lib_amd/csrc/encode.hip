@@ -374,8 +374,10 @@ bool dict_words(const Params &prm, const StreamDesc &sd, bool stored) {
          dict_enabled();
 }
 struct MatchSearch {   // what the call's streams need, gathered by match_job
-  bool any_hist = false, any_parts = false, any_dict = false, any_cdict = false, cdict_std = false;
-  const uint32_t *cdict_tab = nullptr;
+  bool any_hist = false, any_parts = false, any_dict = false, any_cdict = false;
+  // a call's streams may hold different dictionaries (a batch of BrotliEncoder sessions): some
+  // stream wants the custom dictionary's tail copies / some stream has a prepared dictionary's index
+  bool any_tail = false, any_lookup = false;
 };
 // the Job fields the match search reads, from the stream's description
 void match_job(Job &jb, const Params &prm, const StreamDesc &sd, MatchSearch &ms) {
@@ -398,8 +400,14 @@ void match_job(Job &jb, const Params &prm, const StreamDesc &sd, MatchSearch &ms
     jb.cdict_len = sd.cdict_len;
     jb.cdict_tail4 = sd.cdict_tail4;
     ms.any_cdict = true;
-    // (one dictionary a call: every stream that has one has the same)
-    if (sd.cdict_std) ms.cdict_std = true, ms.cdict_tab = sd.cdict_tab, jb.cdict_std = 1;
+    // (the dictionary is the stream's own: Job.cdict_tab, Job.cdict_std)
+    if (sd.cdict_std) {
+      jb.cdict_std = 1;
+      jb.cdict_tab = sd.cdict_tab;
+      if (jb.cdict_tab) ms.any_lookup = true;
+    } else {
+      ms.any_tail = true;
+    }
   }
   jb.dict = dict_words(prm, sd, jb.uncompressed != 0) ? 1 : 0;
   jb.dict_span = dict_span();
@@ -419,9 +427,9 @@ void launch_match_search(hipStream_t st, const Params &prm, const MatchSearch &m
   const uint32_t max_dist = (1u << prm.lgwin) - 16;
   launch_find_matches(st, d_jobs, d_seg_job, d_seg_ref, skeys, svals, total, depth, max_dist, ms.any_hist, ms.any_parts, matches);
   if ((passes & kPassWords) && dd) launch_dict_matches(st, d_jobs, k, dict_span(), dd->tab, dd->data, matches);
-  if ((passes & kPassTail) && ms.any_cdict && !ms.cdict_std) launch_cdict_matches(st, d_jobs, d_seg_job, total, matches);
+  if ((passes & kPassTail) && ms.any_tail) launch_cdict_matches(st, d_jobs, d_seg_job, total, matches);
   if ((passes & kPassNear) && near_scan(prm)) launch_near_matches(st, d_jobs, d_seg_job, d_seg_ref, total, max_dist, ms.any_hist, ms.any_parts, matches);
-  if ((passes & kPassLookup) && ms.cdict_tab) launch_cdict_lookup(st, d_jobs, d_seg_job, total, ms.cdict_tab, hash_bytes(prm), matches);
+  if ((passes & kPassLookup) && ms.any_lookup) launch_cdict_lookup(st, d_jobs, d_seg_job, total, hash_bytes(prm), matches);
 }
 
 // Encode a group of streams into d_out (packed from out_pos; returns the per-stream sizes).
@@ -700,7 +708,7 @@ int encode_group(mib_ctx *ctx, const Params &prm, const StreamDesc *sd, size_t k
     if (two_pass && rep_pass(prm)) launch_rep(st, d_jobs, d_segs, nsegs, model, raw, cmd_pos);   // (cmd_pos: scratch until codes)
     launch_ring_scan(st, d_jobs, (int)k, d_segs, nsegs, raw, push);
     launch_codes(st, d_jobs, d_segs, d_mbs, nsegs, raw, cmds, cmd_pos, units, unit_h);
-    launch_dist_ring(st, d_jobs, (int)k, d_segs, cmds);
+    launch_dist_ring(st, d_jobs, (int)k, d_segs, cmds, cmd_pos);
     tm.stop();
     tm.start("block_split");
     fk.fork();
@@ -942,6 +950,15 @@ struct DevDict {
   }
 };
 
+// a prepared dictionary on a stream: resident, with its index for the call's keys (hb bytes)
+void attach_handle(StreamDesc &sd, const mib_dictionary *dh, int hb) {
+  sd.cdict = dh->d_data;
+  sd.cdict_len = (uint32_t)dh->n;
+  sd.cdict_tail4 = 0;
+  sd.cdict_std = true;
+  sd.cdict_tab = hb == 4 ? dh->tab4 : hb == 6 ? dh->tab6 : nullptr;
+}
+
 constexpr uint64_t kMaxChunk = 256ull << 20;   // BrotliEncoder: the largest device encode it waits for
 // BrotliEncoder: update() pieces up to half this size gather in a pinned host stage and reach
 // the device one stage at a time (a copy call and its wait cost ~70 us: C5's 1 MiB pieces
@@ -981,6 +998,9 @@ struct mib_encoder {
   uint32_t *tab = nullptr;
   std::vector<uint8_t> dict;      // customDictionary (the encoder's own copy) and its device copy
   DevDict ddict;
+  // or a prepared dictionary (mib_encoder_new_dictionary): the handle's device bytes and index,
+  // used in place; the encoder holds a reference (dictionary.h) and no copy
+  const mib_dictionary *handle = nullptr;
   uint8_t *stage = nullptr;       // small update() pieces gather here (pinned host memory) ...
   uint64_t staged = 0;            // ... these many bytes, still to go behind the pending input
 };
@@ -1080,12 +1100,7 @@ static int encode_host(const mib_span *in, size_t k, const mib_enc_opts *o, cons
   for (size_t i = 0; i < k; i++) {
     fill_desc(sd[i], d_in + ioff[i], in[i].size, prm, true);
     dd.attach(sd[i]);
-    if (dh) {   // a prepared dictionary: resident, with its index for this call's keys
-      sd[i].cdict = dh->d_data;
-      sd[i].cdict_len = (uint32_t)dh->n;
-      sd[i].cdict_std = true;
-      sd[i].cdict_tab = hb == 4 ? dh->tab4 : hb == 6 ? dh->tab6 : nullptr;
-    }
+    if (dh) attach_handle(sd[i], dh, hb);
   }
   std::vector<uint64_t> ooff(k + 1, 0);
   rc = encode_streams(c, o, sd.data(), k, d_out, cap, ooff.data(), nullptr, st);
@@ -1110,6 +1125,7 @@ static int encode_host(const mib_span *in, size_t k, const mib_enc_opts *o, cons
 // `need` bytes of history + pending input (+ the zero tail the kernels read past a chunk).
 static int encoder_room(mib_encoder *e, int dev, uint64_t need, hipStream_t st) {
   if (e->device >= 0 && e->device != dev) return MIB_E_INVALID_ARG;
+  if (e->handle && e->handle->device != dev) return MIB_E_INVALID_ARG;
   e->device = dev;
   need += 320;
   if (e->buf_cap < need) {   // first use, a grown chunk, or one large update()
@@ -1133,7 +1149,7 @@ static int encoder_room(mib_encoder *e, int dev, uint64_t need, hipStream_t st) 
     if (hipMalloc(&e->tab, sizeof(uint32_t) * kHistWays << kHashBits) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
     CK(hipMemsetAsync(e->tab, 0xFF, sizeof(uint32_t) * kHistWays << kHashBits, st));
   }
-  if (!e->ddict.d && e->dict.size() >= 4) {
+  if (!e->handle && !e->ddict.d && e->dict.size() >= 4) {   // (a handle is resident: nothing to upload)
     const int r = e->ddict.upload(e->dict.data(), e->dict.size(), st);
     if (r) return r;
   }
@@ -1161,6 +1177,7 @@ static int encoder_run(mib_ctx *c, mib_encoder *const *es, const uint64_t *ns, c
                        mib_buf *const *outs) {
   hipStream_t st = (hipStream_t)mib_ctx_stream_of(c);
   const Params prm = make_params(&es[0]->opts);
+  const int hb = hash_bytes(prm);
   uint64_t cap = 0;
   for (size_t i = 0; i < k; i++) cap += out_bound(ns[i]);
   uint8_t *d_out = mib_ctx_stage(c, 3, cap + 64);
@@ -1185,7 +1202,8 @@ static int encoder_run(mib_ctx *c, mib_encoder *const *es, const uint64_t *ns, c
     sd[i].win_abs = (uint32_t)std::min<uint64_t>(e->abs, 1u << 24);
     sd[i].hist_tab = e->tab;
     sd[i].out_base = e->obytes;
-    e->ddict.attach(sd[i]);
+    if (e->handle) attach_handle(sd[i], e->handle, hb);
+    else e->ddict.attach(sd[i]);
   }
   std::vector<uint64_t> ooff(k + 1, 0);
   std::vector<int32_t> dcs(4 * std::max<size_t>(k, 1));
@@ -1298,11 +1316,17 @@ int mib_dictionary_new(const uint8_t *data, size_t n, mib_dictionary **out) {
   *out = d;
   return 0;
 }
-void mib_dictionary_free(mib_dictionary *d) {
-  if (!d) return;
+// (internal, dictionary.h) a session's reference
+void mib_dictionary_ref(const mib_dictionary *d) { const_cast<mib_dictionary *>(d)->refs.fetch_add(1, std::memory_order_relaxed); }
+void mib_dictionary_unref(const mib_dictionary *d) {
+  mib_dictionary *m = const_cast<mib_dictionary *>(d);
+  if (m->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
   DefaultLock use;   // (no call of the default context is using it)
-  hipSetDevice(d->device);
-  dictionary_release(d);
+  hipSetDevice(m->device);
+  dictionary_release(m);
+}
+void mib_dictionary_free(mib_dictionary *d) {
+  if (d) mib_dictionary_unref(d);   // the creator's reference; sessions made with d keep theirs
 }
 uint64_t mib_dictionary_size(const mib_dictionary *d) { return d ? d->n : 0; }
 
@@ -1466,6 +1490,15 @@ mib_encoder *mib_encoder_new(const mib_enc_opts *o) {
   return e;
 }
 
+mib_encoder *mib_encoder_new_dictionary(const mib_enc_opts *o, const mib_dictionary *d) {
+  if (!d || (o && o->dict)) return nullptr;   // (before any device work, and before d is read)
+  mib_encoder *e = mib_encoder_new(o);
+  if (!e) return nullptr;
+  mib_dictionary_ref(d);
+  e->handle = d;
+  return e;
+}
+
 static bool same_opts(const mib_enc_opts &a, const mib_enc_opts &b) {
   const Params x = make_params(&a), y = make_params(&b);
   return x.quality == y.quality && x.lgwin == y.lgwin && x.npostfix == y.npostfix && x.ndirect == y.ndirect;
@@ -1582,6 +1615,7 @@ void mib_encoder_free(mib_encoder *e) {
     if (e->tab) hipFree(e->tab);
     e->ddict.release();
   }
+  if (e->handle) mib_dictionary_unref(e->handle);
   if (e->stage) {
     hipHostFree(e->stage);
     g_stage_bytes.fetch_sub(kStage);

@@ -1199,6 +1199,10 @@ int mib_decode_batch(const mib_span *in, size_t k, mib_buf *out, int *status) {
 struct mib_decoder : mib::StreamSession {
   std::vector<uint8_t> dict;          // customDictionary until the device copy exists
   bool has_dict = false;
+  // or a prepared dictionary (mib_decoder_new_dictionary): has_dict, d_dict is the handle's own
+  // device memory (never freed here), no host copy; the session holds a reference (dictionary.h)
+  const mib_dictionary *handle = nullptr;
+  uint64_t dict_len() const { return handle ? handle->n : has_dict ? dict.size() : 0; }
   uint8_t *d_dict = nullptr, *d_buf = nullptr, *d_in = nullptr;
   uint64_t in_cap = 0;
   mib::StreamCkpt *d_ck = nullptr;    // the window dump lives here; every launch carries the head beside its job
@@ -1213,7 +1217,7 @@ constexpr uint64_t kStreamScratch = (mib::kDecodeScratchBytes + 255) & ~(uint64_
 
 void decoder_release(mib_decoder *d) {
   hipSetDevice(d->device);
-  for (void *p : {(void *)d->d_dict, (void *)d->d_buf, (void *)d->d_in, (void *)d->d_ck})
+  for (void *p : {(void *)(d->handle ? nullptr : d->d_dict), (void *)d->d_buf, (void *)d->d_in, (void *)d->d_ck})
     if (p) hipFree(p);
   d->d_dict = d->d_buf = d->d_in = nullptr;
   d->d_ck = nullptr;
@@ -1230,7 +1234,10 @@ int decoder_open(mib_decoder *d, mib_ctx *c, uint8_t first) {
   d->buf_cap = mib::stream_buf_cap(lgwin, d->out_window);
   if (hipMalloc((void **)&d->d_buf, d->buf_cap) != hipSuccess || hipMalloc((void **)&d->d_ck, sizeof(mib::StreamCkpt)) != hipSuccess)
     return MIB_E_OUT_OF_MEMORY;
-  if (d->has_dict) {
+  if (d->handle) {   // resident: the handle's bytes, in place
+    if (d->handle->device != c->device) return MIB_E_INVALID_ARG;
+    d->d_dict = d->handle->d_data;
+  } else if (d->has_dict) {
     if (hipMalloc((void **)&d->d_dict, d->dict.size() + 16) != hipSuccess) return MIB_E_OUT_OF_MEMORY;
     const mib::HostPiece up{d->d_dict, d->dict.data(), d->dict.size()};
     int rc = mib::ctx_upload(c, c->stream, &up, 1);
@@ -1368,9 +1375,9 @@ struct RoundsDev {
       const mib_decoder *s = d[jobs[a]];
       // the history to the buffer's front: the launch needs out_window + slack behind pos
       if (plans[a].move) moves.push_back(mib::MoveDesc{s->d_buf, plans[a].move, s->ck.e.pos});
-      // (in, in_len, buf, buf_cap, out_limit, dict, dict_len, ck, lgwin, final; the kernel's fields 0)
+      // (in, in_len, buf, buf_cap, out_limit, dict, dict_len, ck, lgwin, final, status, dict_std; the kernel's fields 0)
       const mib::StreamJob j{s->d_in, s->in_len, s->d_buf, s->buf_cap, plans[a].out_limit, s->d_dict,
-                             s->has_dict ? s->dict.size() : 0, s->d_ck, s->lgwin, final, 0, 0, 0, 0, 0};
+                             s->dict_len(), s->d_ck, s->lgwin, final, 0, s->handle ? 1 : 0, 0, 0, 0};
       memcpy(host.data() + a * sizeof(j), &j, sizeof(j));
       memcpy(host.data() + heads_at + a * kCkHead, &s->ck, kCkHead);
     }
@@ -1642,6 +1649,16 @@ mib_decoder *mib_decoder_new(const mib_dec_opts *o) {
   return d;
 }
 
+mib_decoder *mib_decoder_new_dictionary(const mib_dec_opts *o, const mib_dictionary *h) {
+  if (!h || (o && o->dict)) return nullptr;   // (before any device work, and before h is read)
+  mib_decoder *d = mib_decoder_new(o);
+  if (!d) return nullptr;
+  mib_dictionary_ref(h);
+  d->handle = h;
+  d->has_dict = true;
+  return d;
+}
+
 // a lone session's calls are the batch calls with k = 1 (`out` is emptied here: a call that
 // finds no device returns before it touches its slots)
 int mib_decoder_update(mib_decoder *d, const uint8_t *in, size_t n, mib_buf *out) {
@@ -1678,6 +1695,7 @@ void mib_decoder_free(mib_decoder *d) {
     DefaultUse use;
     decoder_release(d);
   }
+  if (d->handle) mib_dictionary_unref(d->handle);
   delete d;
 }
 

@@ -56,7 +56,8 @@ struct StreamJob {
   int32_t lgwin;
   int32_t final;           // the end of `in` is the end of the stream (finish())
   int32_t status;          // out: kStream* or an error code
-  int32_t reserved;
+  int32_t dict_std;        // DecJob::dict_std: 1 -- `dict` is a prepared dictionary (mib_decoder_new_dictionary),
+                           // a copy may lie anywhere inside it; 0 -- the reference's rule (customDictionary)
   int64_t out_pos;         // out: output is valid up to here (the checkpoint's pos; the end when finished)
   int64_t need_len;        // out, with kStreamNeedInput: no launch gets further before in_len reaches this (0: unknown)
   int64_t redone;          // out: output bytes decoded behind the checkpoint, which the next launch decodes again
@@ -68,7 +69,10 @@ struct StreamJob {
 // copy longer than that is refused before it stores (-9), an uncompressed metablock is its
 // length.  MLEN <= 2^24 (six nibbles).  A dictionary word may pass the metablock's end by its
 // transform's affixes (< 64 bytes) before the -10.  A compound-dictionary copy is checked
-// against the capacity before it stores (decode_core.inc, ST_COPY_FROM_COMPOUND).
+// against the capacity before it stores (decode_core.inc, ST_COPY_FROM_COMPOUND); under either
+// rule for its address (StreamJob::dict_std): a prepared dictionary's copy that passes its
+// dictionary's end is refused earlier still (-9, use_dictionary), so that check only ever ends
+// such a session in the metablock below zero (-10).
 constexpr uint64_t kStreamMaxMlen = 1ull << 24;
 constexpr uint64_t kStreamSlack = kStreamMaxMlen + 64 + 192;   // + the kernels' read slack
 constexpr uint64_t kStreamMinWindow = 64ull << 10;

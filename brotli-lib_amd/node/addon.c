@@ -159,11 +159,14 @@ static void encoder_finalize(napi_env env, void *data, void *hint) {
   mib_encoder_free((mib_encoder *)data);
 }
 
-/* encoderNew(quality, lgwin, mode, dictionary|null, streamChunk) -> external handle (the
- * encoder copies the dictionary) */
+static int get_dictionary(napi_env env, napi_value v, mib_dictionary **d);
+
+/* encoderNew(quality, lgwin, mode, customDictionary|null, streamChunk, dictionary|null) -> external
+ * handle (the encoder copies a customDictionary; of a BrotliDictionary it takes a reference of its
+ * own, mib_encoder_new_dictionary, so the session outlives the dictionary's close()) */
 static napi_value js_encoder_new(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5], out;
+  size_t argc = 6;
+  napi_value argv[6], out;
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   mib_enc_opts o;
   mib_enc_opts_default(&o);
@@ -175,7 +178,10 @@ static napi_value js_encoder_new(napi_env env, napi_callback_info info) {
   else o.dict = NULL;
   const int64_t sc = argc > 4 ? get_i64(env, argv[4], 0) : 0;
   o.stream_chunk = sc > 0 ? (uint64_t)sc : 0;
-  mib_encoder *e = mib_encoder_new(&o);
+  mib_dictionary *hd = NULL;
+  if (argc > 5 && get_dictionary(env, argv[5], &hd)) return NULL;
+  if (hd && o.dict) return throw_code(env, MIB_E_INVALID_ARG);
+  mib_encoder *e = hd ? mib_encoder_new_dictionary(&o, hd) : mib_encoder_new(&o);
   if (!e) return throw_code(env, MIB_E_OUT_OF_MEMORY);
   CHECK(env, napi_create_external(env, e, encoder_finalize, NULL, &out));
   return out;
@@ -232,11 +238,12 @@ static napi_value throw_decoder(napi_env env, int rc, mib_buf *b) {
   return throw_code(env, rc);
 }
 
-/* decoderNew(dictionary|null, maxOutputSize|-1, outWindow|0) -> external handle (the decoder
- * copies the dictionary) */
+/* decoderNew(customDictionary|null, maxOutputSize|-1, outWindow|0, dictionary|null) -> external
+ * handle (the decoder copies a customDictionary; of a BrotliDictionary it takes a reference of its
+ * own, mib_decoder_new_dictionary) */
 static napi_value js_decoder_new(napi_env env, napi_callback_info info) {
-  size_t argc = 3;
-  napi_value argv[3], out;
+  size_t argc = 4;
+  napi_value argv[4], out;
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   mib_dec_opts o;
   mib_dec_opts_default(&o);
@@ -247,7 +254,10 @@ static napi_value js_decoder_new(napi_env env, napi_callback_info info) {
   o.max_out = mo < 0 ? -1 : mo;
   const int64_t ow = argc > 2 ? get_i64(env, argv[2], 0) : 0;
   o.out_window = ow > 0 ? (uint64_t)ow : 0;
-  mib_decoder *d = mib_decoder_new(&o);
+  mib_dictionary *hd = NULL;
+  if (argc > 3 && get_dictionary(env, argv[3], &hd)) return NULL;
+  if (hd && o.dict) return throw_code(env, MIB_E_INVALID_ARG);
+  mib_decoder *d = hd ? mib_decoder_new_dictionary(&o, hd) : mib_decoder_new(&o);
   if (!d) return throw_code(env, MIB_E_OUT_OF_MEMORY);
   CHECK(env, napi_create_external(env, d, decoder_finalize, NULL, &out));
   return out;

@@ -11,13 +11,15 @@ export type EncoderMode = (typeof EncoderMode)[keyof typeof EncoderMode]
 
 /** extension (brotli_amd.h mib_dictionary): shared bytes uploaded to the GPU and indexed there
  *  once. Copies may come from anywhere in it (customDictionary: its tail only), so a stream
- *  written with one decodes with one of the same bytes. Not for BrotliEncoder / BrotliDecoder. */
+ *  written with one decodes with one of the same bytes. A BrotliEncoder / BrotliDecoder made with
+ *  it (options.dictionary) holds a reference of its own and keeps working after close(). */
 export declare class BrotliDictionary {
   constructor(data: Uint8Array | Int8Array)
   /** the dictionary's length in bytes */
   readonly size: number
   readonly closed: boolean
-  /** frees the device memory; waits for pending async calls that use the dictionary */
+  /** drops this object's reference to the device memory (it goes once no session holds the
+   *  dictionary either); waits for pending async calls that use the dictionary */
   close(): void
 }
 
@@ -32,8 +34,8 @@ export interface BrotliEncodeOptions {
   /** extension: the encoder side of BrotliDecodeOptions.customDictionary; the stream decodes
    *  with (and only with) the same dictionary */
   customDictionary?: Uint8Array | Int8Array
-  /** extension: a prepared dictionary (not together with customDictionary, not with gpus; not
-   *  for BrotliEncoder) */
+  /** extension: a prepared dictionary (not together with customDictionary, not with gpus);
+   *  new BrotliEncoder({dictionary}) takes it too, with the same errors */
   dictionary?: BrotliDictionary
 }
 
@@ -64,6 +66,9 @@ export interface BrotliDecoderOptions {
   customDictionary?: Uint8Array | Int8Array
   /** output bytes per device pass, default 16 MiB, clamped to 64 KiB .. 512 MiB */
   outWindow?: number
+  /** extension: the BrotliDictionary the stream was written with (not together with
+   *  customDictionary): copies from anywhere in it are valid, as in brotliDecode */
+  dictionary?: BrotliDictionary
 }
 
 /** extension (the reference decodes in one shot only): the decode side of BrotliEncoder. The

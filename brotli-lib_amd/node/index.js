@@ -40,10 +40,13 @@ function toU8(b) {
 
 // BrotliDictionary (extension; brotli_amd.h mib_dictionary): shared bytes uploaded to the GPU and
 // indexed there once.  Pass it as options.dictionary to brotliEncode, brotliEncodeBatch,
-// brotliEncodeBatchAsync, brotliDecode and brotliDecodeBatchAsync.  Copies may come from anywhere
-// in it, so a stream written with one decodes with one of the same bytes (not with
-// customDictionary).  close() frees the device memory; while an async call that uses the
-// dictionary is pending, close() waits for it to settle.  size: the dictionary's length.
+// brotliEncodeBatchAsync, brotliDecode and brotliDecodeBatchAsync, and to new BrotliEncoder /
+// new BrotliDecoder.  Copies may come from anywhere in it, so a stream written with one decodes
+// with one of the same bytes (not with customDictionary).  close() drops this object's reference
+// to the device memory; while an async call that uses the dictionary is pending, close() waits
+// for it to settle.  A BrotliEncoder / BrotliDecoder made with the dictionary holds a reference
+// of its own: it keeps working after close(), and the memory goes with the last of them.
+// size: the dictionary's length.
 class BrotliDictionary {
   constructor(data) {
     const d = data instanceof Uint8Array ? data : new Uint8Array(data.buffer, data.byteOffset, data.byteLength)
@@ -105,7 +108,11 @@ class BrotliEncoder {
     const [q, lg, m] = clampOptions(options)
     // options.streamChunk (extension): throughput mode, see brotli_amd.h mib_enc_opts.stream_chunk
     const sc = options && options.streamChunk ? Math.max(0, options.streamChunk) : 0
-    this._h = native.encoderNew(q, lg, m, dictOf(options), sc)
+    // options.dictionary (extension): a BrotliDictionary, errors as brotliEncode's; the session
+    // copies from anywhere in it and its stream decodes with new BrotliDecoder({dictionary})
+    const hd = handleOf(options)
+    this._dictionary = hd
+    this._h = native.encoderNew(q, lg, m, hd ? null : dictOf(options), sc, hd ? hd._h : null)
   }
   update(input) {
     return toU8(native.encoderUpdate(this._h, input))
@@ -149,14 +156,18 @@ function brotliDecode(buffer, options) {
 // BrotliEncoder.  update(chunk) takes the next bytes of one stream, cut anywhere, and returns
 // the bytes they complete; finish() declares the input ended and returns the rest, or throws
 // the decoder's error for an incomplete stream; finished: the last metablock is decoded.
-// options: customDictionary, maxOutputSize (total), outWindow (output bytes per device pass).
+// options: customDictionary, maxOutputSize (total), outWindow (output bytes per device pass),
+// dictionary (a BrotliDictionary, not with customDictionary: copies from anywhere in it).
 class BrotliDecoder {
   constructor(options) {
     const o = options || {}
+    const hd = handleOf(o)
+    this._dictionary = hd
     const d = o.customDictionary
     const dict = d ? (d instanceof Uint8Array ? d : new Uint8Array(d.buffer, d.byteOffset, d.byteLength)) : null
     this._max = o.maxOutputSize
-    this._h = native.decoderNew(dict, o.maxOutputSize === undefined ? -1 : o.maxOutputSize, o.outWindow ? Math.max(0, o.outWindow) : 0)
+    this._h = native.decoderNew(dict, o.maxOutputSize === undefined ? -1 : o.maxOutputSize, o.outWindow ? Math.max(0, o.outWindow) : 0,
+      hd ? hd._h : null)
   }
   _call(f, ...args) {
     try {

@@ -183,6 +183,11 @@ def _L():
                                                     ctypes.c_void_p, ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_decode_batch_dictionary.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int64,
                                                     ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
+        if hasattr(lib, 'mib_encoder_new_dictionary'):   # (a BROTLI_AMD_LIB build may predate it)
+            lib.mib_encoder_new_dictionary.argtypes = [ctypes.POINTER(_Opts), ctypes.c_void_p]
+            lib.mib_encoder_new_dictionary.restype = ctypes.c_void_p
+            lib.mib_decoder_new_dictionary.argtypes = [ctypes.POINTER(_DecOpts), ctypes.c_void_p]
+            lib.mib_decoder_new_dictionary.restype = ctypes.c_void_p
         lib.mib_encode_batch_n.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.POINTER(_Opts), ctypes.c_int,
                                            ctypes.POINTER(_Buf), ctypes.POINTER(ctypes.c_int)]
         lib.mib_decode_batch_n.argtypes = [ctypes.POINTER(_Span), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_Buf),
@@ -330,9 +335,12 @@ class Dictionary:
     """A prepared dictionary (mib_dictionary, brotli_amd.h): bytes that many small, similar
     buffers are compressed against, uploaded and indexed on the GPU once.  Pass it as
     `dictionary=` to encode_batch / decode_batch or as options['dictionary'] to brotliEncode /
-    brotliDecode.  Copies may come from anywhere in it, so a stream written with one decodes
-    only with one (of the same bytes).  close() frees the device memory; the object must stay
-    open while a call uses it.  len() is the dictionary's size."""
+    brotliDecode / BrotliEncoder / BrotliDecoder.  Copies may come from anywhere in it, so a
+    stream written with one decodes only with one (of the same bytes).  close() drops this
+    object's reference: the object must stay open while a one-shot call uses it and may not be
+    given to a new call or session afterwards, but the sessions already made with it hold
+    references of their own and keep working -- the device memory goes with the last of them.
+    len() is the dictionary's size."""
 
     def __init__(self, data):
         d = _bytes(data)
@@ -369,7 +377,8 @@ class Dictionary:
 
 
 def _dictionary(dictionary, options):
-    """the handle of a `dictionary` argument; both kinds of dictionary at once is an error"""
+    """the handle of a `dictionary` argument; both kinds of dictionary at once is an error
+    (checked before the library is loaded: no device needed to be told)"""
     if not isinstance(dictionary, Dictionary):
         raise TypeError('dictionary must be a brotli_amd.Dictionary')
     if isinstance(options, dict) and options.get('customDictionary') is not None:
@@ -391,10 +400,19 @@ def brotliEncode(input, options=None):
 
 
 class BrotliEncoder:
-    """Streaming encoder: update() returns the newly completed bytes, finish() the rest."""
+    """Streaming encoder: update() returns the newly completed bytes, finish() the rest.
+    options['dictionary'] (a Dictionary; not with 'customDictionary'): the session copies from
+    anywhere in the prepared dictionary, in place on the device, and holds a reference to it --
+    its stream decodes through decode_batch(dictionary=) and BrotliDecoder({'dictionary': ...})."""
 
     def __init__(self, options=None):
-        self._h = _L().mib_encoder_new(ctypes.byref(_opts(options)))
+        self._dictionary = None
+        if isinstance(options, dict) and options.get('dictionary') is not None:
+            h = _dictionary(options['dictionary'], options)
+            self._dictionary = options['dictionary']
+            self._h = _L().mib_encoder_new_dictionary(ctypes.byref(_opts(options)), h)
+        else:
+            self._h = _L().mib_encoder_new(ctypes.byref(_opts(options)))
         if not self._h:
             raise BrotliError('brotli_amd: encoder creation failed')
 
@@ -421,7 +439,8 @@ class BrotliEncoder:
 
 def encoder_update_batch(encoders, chunks):
     """Advance independent BrotliEncoders by one chunk each in one GPU launch sequence;
-    returns each encoder's update() result."""
+    returns each encoder's update() result.  The encoders may hold different dictionaries
+    (options['dictionary'], 'customDictionary') or none: each chunk is searched against its own."""
     k = len(encoders)
     keep = [_in(b) for b in chunks]
     hs = (ctypes.c_void_p * k)(*[e._h for e in encoders])
@@ -469,11 +488,18 @@ class BrotliDecoder:
     finish() declares the input ended and returns the rest, raising the reference decoder's
     error for an incomplete stream; `finished` is true once the last metablock is decoded.
     options: {'customDictionary', 'maxOutputSize' (total), 'outWindow' (output bytes per device
-    pass, default 16 MiB, 64 KiB .. 512 MiB)}.  Bytes behind the stream's end raise code -17;
+    pass, default 16 MiB, 64 KiB .. 512 MiB), 'dictionary' (a Dictionary, not with
+    'customDictionary': copies from anywhere in it are valid, as in decode_batch(dictionary=);
+    the session reads it in place and holds a reference)}.  Bytes behind the stream's end raise code -17;
     after an error every call raises it again."""
 
     def __init__(self, options=None):
         options = options or {}
+        self._dictionary = None
+        handle = None
+        if options.get('dictionary') is not None:
+            handle = _dictionary(options['dictionary'], options)
+            self._dictionary = options['dictionary']
         o = _DecOpts(None, 0, -1, 0)
         if options.get('customDictionary') is not None:
             d = _bytes(options['customDictionary'])
@@ -483,7 +509,10 @@ class BrotliDecoder:
         if options.get('outWindow') is not None:
             o.out_window = max(0, int(options['outWindow']))
         self._max_out = o.max_out
-        self._h = _L().mib_decoder_new(ctypes.byref(o))
+        if handle is not None:
+            self._h = _L().mib_decoder_new_dictionary(ctypes.byref(o), handle)
+        else:
+            self._h = _L().mib_decoder_new(ctypes.byref(o))
         if not self._h:
             raise BrotliError('brotli_amd: decoder creation failed')
 
@@ -549,7 +578,8 @@ def decoder_update_batch(decoders, chunks):
     """Advance many BrotliDecoder sessions by one chunk each: a round is one decode launch over
     every session that still has work (mib_decoder_update_batch).  Returns a list with, per
     slot, the bytes decoder.update(chunk) alone would have returned, or the BrotliError it would
-    have raised (not raised here: the other sessions go on).  The decoders must be distinct."""
+    have raised (not raised here: the other sessions go on).  The decoders must be distinct;
+    they may hold different dictionaries (options['dictionary'], 'customDictionary') or none."""
     k = len(decoders)
     if len(chunks) != k:
         raise ValueError('decoder_update_batch: %d decoders, %d chunks' % (k, len(chunks)))

@@ -215,13 +215,19 @@ int mib_decode_batch_n(const mib_span *in, size_t k, int n_gpus, mib_buf *out, i
  * (two tables of 4 MiB: 4-byte keys for FONT mode, 6-byte keys for GENERIC / TEXT; a table is
  * left out where the dictionary is shorter than its key).  It is immutable, may be used by any
  * number of calls and threads (the calls serialise on the default context, as every host entry
- * point does) and must outlive the calls that use it.  n may be 0 .. 2^31 - 1; a dictionary of
+ * point does) and must outlive the calls that use it (a session made with it holds a reference
+ * of its own, below).  n may be 0 .. 2^31 - 1; a dictionary of
  * fewer than 4 bytes is attached (it shifts the addresses of the static dictionary's words, as
  * any custom dictionary does) but offers no copies.
  *   mib_dictionary_new   0; MIB_E_INVALID_ARG (NULL out, NULL data with n > 0, n >= 2^31: before
  *                        any device work), MIB_E_NO_DEVICE, MIB_E_OUT_OF_MEMORY; on every error
  *                        *out is NULL
  *   mib_dictionary_free  NULL is harmless;  mib_dictionary_size: n, 0 for NULL
+ * Lifetime: the handle is reference counted.  mib_dictionary_new holds one reference, which
+ * mib_dictionary_free drops; every session made with the handle (below) holds one, which
+ * mib_encoder_free / mib_decoder_free drop.  The device memory goes with the last reference, under
+ * the default context's lock.  After mib_dictionary_free the handle may not be given to any new
+ * call; the sessions that already hold it keep working.
  * Addressing ("standard"): the decoder's arithmetic is that of mib_decode's customDictionary,
  * address = distance - max distance - 1 - n, a negative value a copy from dictionary offset
  * a = -address - 1; but with a handle the copy is valid whenever a + length <= n (else -9), where
@@ -254,8 +260,29 @@ int mib_decode_batch_n(const mib_span *in, size_t k, int n_gpus, mib_buf *out, i
  * mib_woff2_decode_batch's: everything about one stream is that slot's code and leaves the others
  * running, a failed slot is {NULL, 0}.  max_out (-1: none) applies to every slot as mib_decode's
  * does: MIB_E_OUTPUT_LIMIT, no data, the offending size in out[i].size.  Streams of fewer than 64
- * bytes and quality 0 are stored, as without a dictionary.  BrotliEncoder / BrotliDecoder sessions,
- * the mib_ctx_* and the _n calls take no handle. */
+ * bytes and quality 0 are stored, as without a dictionary.  The mib_ctx_* and the _n calls take no
+ * handle.
+ * Sessions (BrotliEncoder / BrotliDecoder with options.dictionary):
+ *   mib_encoder_new_dictionary(o, d), mib_decoder_new_dictionary(o, d)
+ * return NULL for a NULL handle and for o->dict set together with a handle (both before any device
+ * work), else what mib_encoder_new / mib_decoder_new return: an ordinary session, which every entry
+ * point takes unchanged and may mix with other sessions in one call -- sessions with other
+ * handles, with a customDictionary or with none (mib_encoder_update / _finish / _update_batch,
+ * mib_decoder_update / _finish / _update_batch / _finish_batch and the _device forms).  The session
+ * uses the handle's device bytes and index in place: no copy of its own, on the host or the device.
+ * A handle on another device than the default context's: MIB_E_INVALID_ARG from the first call
+ * that needs the device.
+ * The addressing is that of the one-shot calls, with p the position in the whole stream: a stream
+ * a session writes decodes through mib_decode_batch_dictionary and through a decoder session made
+ * with the same bytes; a customDictionary session (mib_dec_opts.dict) answers -9 to its first copy
+ * from the middle, as mib_decode does.
+ * The encoder limits hold per chunk position.  Past stream position 2^lgwin - 16 the window term
+ * of a distance is constant, so from there on the usable span is exactly
+ * MIB_DICTIONARY_MATCH_SPAN(lgwin) bytes at the dictionary's end: about 12 MiB at the default
+ * lgwin 22, 8 MiB at lgwin 23 and 14 bytes at lgwin 24 -- in a long lgwin-24 stream the handle is
+ * all but inert (the data still round-trips).  A streaming chunk gets no static-dictionary words,
+ * so the record's distance limit is 2^24 - 1 throughout, at every quality.  A run of the
+ * dictionary is cut where a chunk ends, as it is at every 64 KiB parse segment. */
 typedef struct mib_dictionary mib_dictionary;
 #define MIB_DICTIONARY_MATCH_SPAN(lgwin) (0xFFFFFEu - ((1u << (lgwin)) - 16u))
 int mib_dictionary_new(const uint8_t *data, size_t n, mib_dictionary **out);
@@ -265,6 +292,8 @@ int mib_encode_batch_dictionary(const mib_span *in, size_t k, const mib_enc_opts
                                 int *status);
 int mib_decode_batch_dictionary(const mib_span *in, size_t k, const mib_dictionary *d, int64_t max_out, mib_buf *out,
                                 int *status);
+mib_encoder *mib_encoder_new_dictionary(const mib_enc_opts *o, const mib_dictionary *d);
+mib_decoder *mib_decoder_new_dictionary(const mib_dec_opts *o, const mib_dictionary *d);
 /* Visible HIP devices (0 without a GPU). */
 int mib_device_count(void);
 /* Diagnostics: the hardware property the match finder's bucket sort relies on for its
